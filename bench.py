@@ -17,7 +17,11 @@ in its own barrier bracket (``sharded.gather_ms``); ``value`` counts the steps o
 per GPU, no collective (RunMultiRayCode.C:29-52).  Timing: W untimed warm-up steps, then K
 steps bracketed by barrier + synchronize, max over ranks.
 
-Also reported (rank 0): the roofline of table_kernel from executed FP64 VALU instructions
+A plain run does only that: set-up, W warm-up steps, the K timed steps, the table of the last
+step written to ``--dump-outputs DIR`` if asked, and the JSON line.
+
+With ``--full`` also reported (rank 0):
+the roofline of table_kernel from executed FP64 VALU instructions
 (profiles/pmc_summary.json) over the live kernel time; the minimizer (cfg3, 1e6 Air2IceRayTracing
 solves) with its own roofline, CPU baseline and parity on a stride of the timed batch; the
 pythonwrapper batch (cfg5, 1e7 Py_TraceIceToAir rows) with parity; the table lookup; the CPU
@@ -113,6 +117,11 @@ class HipBackend:
                    "airice_host_unregister")
 
 
+# the line items of --full beside the headline (each has a --no-ITEM option)
+LINE_ITEMS = ("solve", "trace", "lookup", "multi", "cold", "pcie", "default-grid", "cfg4", "scalar")
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
 def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -121,6 +130,15 @@ def parse(argv=None):
     p.add_argument("--mode", choices=("sharded", "replicas"), default="sharded",
                    help="N>1: one table sharded by TxH rows + RCCL gather (default), or one "
                         "antenna table per GPU")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline table steps, also run the other line items (minimizer, "
+                        "pythonwrapper, lookup, several antennas, cold builds, table to host, "
+                        "default grid, cfg4, scalar latencies), the rooflines and the CPU legs "
+                        "(baselines, parity); the --no-*, --only and --cfg4-only options choose "
+                        "among them.  Without it only the headline is measured")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the table the last timed step built (rank "
+                        "0's slab when N>1) to DIR/table.npy (float32, the 11 columns by ray)")
     p.add_argument("--solve-n", type=int, default=1_000_000)
     p.add_argument("--solve-steps", type=int, default=20)
     p.add_argument("--no-cpu", action="store_true", help="skip the CPU legs (baselines, parity)")
@@ -164,12 +182,36 @@ def parse(argv=None):
                    help="run the headline table steps and this one line item only, no CPU legs "
                         "(per-workload rocprofv3 summaries, tools/gpu_profiles.sh)")
     a = p.parse_args(argv)
+    if not a.full:
+        if a.only is not None or a.cfg4_only:
+            p.error("--only and --cfg4-only choose among the line items of --full")
+        a.no_cpu = True
+        for item in LINE_ITEMS:
+            setattr(a, "no_" + item.replace("-", "_"), True)
+    if a.dump_outputs is not None and (a.cfg4_only or (a.gpus > 1 and a.workload == "cfg4")):
+        p.error("--dump-outputs writes the headline cfg2 table; the cfg4 table is not kept")
     if a.only is not None:
         a.no_cpu = True
-        for item in ("solve", "trace", "lookup", "multi", "cold", "pcie", "default-grid", "cfg4",
-                     "scalar"):
+        for item in LINE_ITEMS:
             setattr(a, "no_" + item.replace("-", "_"), item != a.only)
     return a
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: DIR/<name>.npy for each array (float32 / float64 kept, anything else as
+    float64).  When the arrays together exceed DUMP_LIMIT_BYTES, each is cut to its share of the
+    limit: the elements at a fixed, seeded choice of flat indices (sorted), the same from run to
+    run for the same shapes."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v if v.dtype in (np.float32, np.float64)
+                                      else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(v.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(20240607).choice(v.size, size=keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), v)
 
 
 def load_pmc() -> dict:
@@ -546,6 +588,9 @@ def main(argv=None, make_backend=None, json_path=None):
                                   distributed, world, coll_dev)
     value = total_rays / elapsed
     extra = {}
+    if args.dump_outputs is not None and rank == 0:
+        # what the last timed step left in HBM, before any line item builds into the same buffer
+        dump_outputs(args.dump_outputs, {"table": table.cpu().numpy()})
 
     # ---------------------------------------------------------------- minimizer (cfg3)
     solve = None
@@ -884,9 +929,11 @@ def main(argv=None, make_backend=None, json_path=None):
         if isinstance(extra.get("scalar_latency_us"), dict):
             extra["scalar_latency_us"]["cpu_oracle_per_call_us"] = scalar_cpu_per_call(om, og, ot)
 
-    roof = counter_roofline("table_kernel_cfg4" if cfg4_headline else "table_kernel", n_local,
-                            kern_ms, pmc, 44.0)
-    roof["ocml_priced"] = ocml_priced(grid, n_local, kern_ms) if kern_ms else None
+    roof = None
+    if args.full:
+        roof = counter_roofline("table_kernel_cfg4" if cfg4_headline else "table_kernel", n_local,
+                                kern_ms, pmc, 44.0)
+        roof["ocml_priced"] = ocml_priced(grid, n_local, kern_ms) if kern_ms else None
 
     if rank == 0:
         if cfg4_headline:

@@ -164,12 +164,19 @@ def test_one_query_host_calls_reject_null_arguments():
 
 
 def test_launch_counters():
-    """airice_launch_count: every documented name answers (0 here: no kernel ran on this CPU
-    box), an unknown one is AIRICE_EINVAL."""
+    """airice_launch_count: every documented name answers -- 0 on a box without a GPU, where no
+    kernel can have run; on a GPU box, where earlier tests of the same process may have launched
+    kernels, the count they left, which a reset hands back and takes to 0 --, an unknown one is
+    AIRICE_EINVAL."""
+    import torch
     from airiceraytracing_amd import _lib
+    gpu = torch.cuda.is_available()
     for name in ("table_kernel", "rays_kernel", "scalar_ray_kernel", "roots_kernel",
                  "scalar_solve_kernel", "out_kernel", "lookup_kernel", "rtf_kernel",
                  "single_ray_kernel", "path_kernel"):
+        n = _lib.launch_count(name)
+        assert n >= 0 if gpu else n == 0, name
+        assert _lib.launch_count(name, reset=True) == n, name
         assert _lib.launch_count(name) == 0, name
     cnt = ctypes.c_int64(7)
     assert _lib.lib().airice_launch_count(b"no_such_kernel", ctypes.byref(cnt), 0) == -1

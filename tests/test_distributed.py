@@ -235,7 +235,7 @@ def _run_bench_ranks(world, argv, json_path, timeout=240):
     return json.loads(lines[0])
 
 
-BENCH8 = ["--gpus", "8", "--steps", "2", "--warmup", "1", "--height-step", "400",
+BENCH8 = ["--gpus", "8", "--full", "--steps", "2", "--warmup", "1", "--height-step", "400",
           "--cfg4-height-step", "2000", "--cfg4-reps", "1", "--no-cpu", "--no-solve", "--no-trace",
           "--no-lookup", "--no-multi", "--no-scalar", "--no-default-grid", "--no-cold", "--no-pcie"]
 
@@ -262,6 +262,47 @@ def test_gloo_world8_bench_flow(tmp_path, cfg4_host):
         assert c4["assemble"] == "rccl" and "IsADirectoryError" in c4["host_assembly_error"]
     else:
         assert c4["assemble"] == "host" and "host_assembly_error" not in c4
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_last_table(tmp_path):
+    """``bench.py --gpus 1 --steps K --warmup W`` without ``--full`` (one gloo rank, the CPU
+    rehearsal backend standing in for the kernels): the JSON line carries the headline figures and
+    no line item, roofline or CPU leg, and ``--dump-outputs DIR`` leaves DIR/table.npy, the float32
+    table of the last timed step, bit for bit the oracle's table of the same grid."""
+    import oracle
+    from tests.conftest import ATMOSPHERE_GZ
+    dump = tmp_path / "dump"
+    line = _run_bench_ranks(1, ["--gpus", "1", "--steps", "3", "--warmup", "1", "--height-step",
+                                "400", "--dump-outputs", str(dump)], str(tmp_path / "bench.json"))
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["metric"] == "solved air->ice rays/sec (MakeRayTracingTable rays)"
+    assert line["unit"] == "rays/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0
+    rays = line["config"]["rays_per_gpu_step"]
+    assert line["value"] == pytest.approx(rays / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    for key in ("roofline", "cpu_baseline", "parity_vs_cpu", "minimizer"):
+        assert line[key] is None, key
+    for key in ("pywrapper_trace", "table_lookup", "multi_antenna_tables", "table_cold",
+                "table_to_host", "table_default_grid", "table_cfg4", "scalar_latency_us"):
+        assert key not in line, key
+    assert sorted(os.listdir(dump)) == ["table.npy"]
+    got = np.load(dump / "table.npy")
+    m = oracle.load_atmosphere(ATMOSPHERE_GZ)
+    g = oracle.grid_init(-20000.0, 300000.0, 400.0, 92.0, 180.0, 0.5)
+    ref = oracle.table_rows(m, g, 0, g.height_steps)
+    assert got.dtype == np.float32 and got.shape == ref.shape == (11, rays)
+    np.testing.assert_array_equal(got.view(np.int32), ref.view(np.int32))
+
+
+def test_bench_line_items_need_full():
+    """``--only`` and ``--cfg4-only`` choose among the line items of ``--full``: without it they
+    are a usage error (exit status 2), not a run that silently measures the headline alone."""
+    import bench
+    for argv in (["--only", "lookup"], ["--cfg4-only"]):
+        with pytest.raises(SystemExit) as e:
+            bench.parse(argv)
+        assert e.value.code == 2
+        assert bench.parse(["--full"] + argv).full
 
 
 BENCH2 = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--height-step", "400",

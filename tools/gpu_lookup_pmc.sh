@@ -1,5 +1,5 @@
 #!/bin/bash
-# Cache counters of the table lookup (bench.py --only lookup: 1e6 random cfg3 queries on the cfg2
+# Cache counters of the table lookup (bench.py --full --only lookup: 1e6 random cfg3 queries on the cfg2
 # table), one rocprofv3 --pmc pass per counter group: L1->L2 read requests and L1 accesses (TCP),
 # L2 requests, hits, misses and fabric reads (TCC).  Writes gpurun_out/lkpmc/lookup_cache.json.
 # With a library argument (tools/gpu_lookup_pmc.sh lib.so) the 1e6 queries of
@@ -22,7 +22,7 @@ for p in 1 2; do
       python $R/tools/lookup_order_probe.py --random-only > $OUT/${NAME}_p$p.log 2>&1 || { echo "pass $p failed"; tail -5 $OUT/${NAME}_p$p.log; exit 1; }
   else
     timeout -s KILL 120 rocprofv3 --pmc $ctr -d $OUT/${NAME}_p$p -o p$p --output-format csv -- \
-      python $R/bench.py --only lookup --no-cpu > $OUT/${NAME}_p$p.log 2>&1 || { echo "pass $p failed"; tail -5 $OUT/${NAME}_p$p.log; exit 1; }
+      python $R/bench.py --full --only lookup --no-cpu > $OUT/${NAME}_p$p.log 2>&1 || { echo "pass $p failed"; tail -5 $OUT/${NAME}_p$p.log; exit 1; }
   fi
 done
 python $R/tools/pmc_summarize.py $OUT/$NAME.json $OUT/${NAME}_p1 $OUT/${NAME}_p2 | grep -i "lookup"

@@ -11,7 +11,7 @@ shift 2
 cd $R && mkdir -p gpurun_out
 OUT=gpurun_out/rehearse${N}_${TAG}
 AIRICE_DIST_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus $N --steps 5 --warmup 2 --cpu-seconds 2 "$@" \
+  --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus $N --full --steps 5 --warmup 2 --cpu-seconds 2 "$@" \
   > $OUT.json 2> $OUT.err || { echo "rehearsal N=$N $TAG failed"; grep -v Warn $OUT.err | tail -30; exit 1; }
 python - <<PY
 import json

@@ -31,7 +31,7 @@ import sys
 SIMDS = 256 * 4
 XCDS = 8
 
-# kernel-name prefix -> (summary key, units per launch) for `bench.py --no-cpu`
+# kernel-name prefix -> (summary key, units per launch) for `bench.py --full --no-cpu`
 UNITS = [("table_kernel", "table_kernel", 858627),
          ("roots_kernel<0>", "roots_kernel", 1000000),
          ("roots_sorted_kernel<0>", "roots_sorted_kernel", 1000000),
@@ -105,7 +105,7 @@ def apply_lookup_calibration(d, calib):
     return d
 
 
-# the cfg4 fine table (`bench.py --cfg4-only`): 97,001 x 8,991 rays in one launch
+# the cfg4 fine table (`bench.py --full --cfg4-only`): 97,001 x 8,991 rays in one launch
 UNITS_CFG4 = [("table_kernel", "table_kernel_cfg4", 872135991)]
 
 
@@ -125,9 +125,9 @@ if __name__ == "__main__":
     src, dst = sys.argv[1], sys.argv[2]
     with open(src) as f:
         raw = json.load(f)
-    out = {"_source": "rocprofv3 --pmc passes of `python bench.py --no-cpu --no-cfg4 "
+    out = {"_source": "rocprofv3 --pmc passes of `python bench.py --full --no-cpu --no-cfg4 "
                       "--no-default-grid --steps 3 --warmup 1 --solve-steps 1` and of `bench.py "
-                      "--cfg4-only` (tools/gpu_pmc.sh), mean per dispatch"}
+                      "--full --cfg4-only` (tools/gpu_pmc.sh), mean per dispatch"}
     sets = [(raw, UNITS)]
     if len(sys.argv) > 3:
         with open(sys.argv[3]) as f:
