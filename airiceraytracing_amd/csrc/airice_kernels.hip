@@ -1,16 +1,27 @@
 // airice_kernels.hip -- gfx950 kernels + stream-ordered launchers of libairice.so.
 //
-//  table_kernel   : one lane per (TxHeight, launch angle) ray of MakeRayTracingTable
-//                   (MultiRayAirIceRefraction.cc:2079-2122 loop body -> GetRayTracingSolutions
-//                   .cc:1796-2017), writes the 11 float table columns (.cc:2101-2111) and,
-//                   optionally, the 18 doubles of dummy[] for parity checks.
-//  rays_kernel    : the same ray for arbitrary (angle, height) lists.
-//  solve_kernel   : one lane per query of Air2IceRayTracing (.cc:1464-1616): bracket set-up,
-//                   the 0.05-degree probe loop, GSL-bisection emulation (tolerance 1e-9,
-//                   40 iterations) over a THD-only evaluator, one full evaluation at the root.
-//                   VARIANT selects MultiRay (dummy[17]) / pythonwrapper (dummy[15]) outputs.
-//  hdtip_kernel   : GetHorizontalDistanceToIntersectionPoint (.cc:945-989), cm in/out.
-//  trace_kernel   : pythonwrapper TraceIceToAir (TraceIceToAir.C:5-73) rows of 10.
+// Forward ray (GetRayTracingSolutions, MultiRayAirIceRefraction.cc:1796-2017):
+//  table_kernel         : one lane per (TxHeight, launch angle) ray of MakeRayTracingTable
+//                         (.cc:2079-2122), writes the 11 float table columns (.cc:2101-2111) and,
+//                         optionally, the 18 doubles of dummy[] for parity checks.
+//  table_multi_kernel   : the same block body for several antennas' tables in one grid.
+//  rowconst_kernel, angle_sines_kernel : fill the per-grid caches of the table launch.
+//  rays_kernel          : the same ray for arbitrary (angle, height) lists.
+//  scalar_ray_kernel    : one ray (n = 1) spread over a wave.
+// Minimizer (Air2IceRayTracing, .cc:1464-1616), two stages around one shared root finder
+// (RootSearch / solve_root, also compiled for the host's one-query calls):
+//  roots_kernel<IN>     : stage 1, one lane per query: bracket set-up, the 0.05-degree probe,
+//                         GSL-bisection replay (tolerance 1e-9, 40 iterations) over a THD-only
+//                         evaluator; each 1,024-query block sorted by straight-line angle in LDS.
+//  group_count_kernel<IN>, group_scatter_kernel<IN>, roots_sorted_kernel<IN> : stage 1 of large
+//                         trace batches, grouped across the whole batch first.
+//  solve_out_kernel<V>  : stage 2, one full evaluation at the parked root; VARIANT selects
+//                         MultiRay (dummy[17]) / pythonwrapper (dummy[15]) outputs.
+//  hdtip_out_kernel     : stage 2 of GetHorizontalDistanceToIntersectionPoint (.cc:945-989), cm.
+//  trace_out_kernel     : stage 2 of pythonwrapper TraceIceToAir (TraceIceToAir.C:5-73), rows of 10.
+//  scalar_solve_kernel<IN, OUT> : one query (n = 1), both stages in one launch on one wave.
+//  lookup_kernel        : the table lookup (.cc:1305-1462, airice_lookup.hpp); a lane that needs
+//                         the reference's minimizer fallback solves it in place.
 //
 // Data layout in HBM: structure-of-arrays, column c of item i at out[c*ld + i], so each
 // wave's store of one column is one contiguous 256 B (f32) / 512 B (f64) segment.
@@ -53,26 +64,8 @@ constexpr int kTraceOutWaves = AIRICE_TRACE_OUT_WAVES;
 #endif
 constexpr int kTableBlock = AIRICE_TABLE_BLOCK;  // (A/B builds: -DAIRICE_TABLE_BLOCK=...)
 constexpr int kTableWaves = 8;
-// debug builds: shader-clock stamps of the one-query kernels (tools/scalar_stamps.py,
-// tools/ray_stamps.py) and the minimizer's evaluation counts by sorted position (tools/wave_evals.py)
-#ifndef AIRICE_SCALAR_STAMP
-#define AIRICE_SCALAR_STAMP 0
-#endif
-#ifndef AIRICE_RAY_STAMP
-#define AIRICE_RAY_STAMP 0
-#endif
-#ifndef AIRICE_NO_CHECK
-#define AIRICE_NO_CHECK 0
-#endif
-#ifndef AIRICE_SORTED_STATS
-#define AIRICE_SORTED_STATS 0
-#endif
-// debug build: roots_kernel writes shader-clock stamps instead of evaluation counts
-// (AIRICE_SOLVE_STATS, 4 ints per query: entry, sorted, inputs at hand, solved; tools/roots_stamps.py)
-#ifndef AIRICE_ROOTS_STAMP
-#define AIRICE_ROOTS_STAMP 0
-#endif
-constexpr int kStatsInts = AIRICE_ROOTS_STAMP == 3 ? 8 : AIRICE_ROOTS_STAMP == 2 ? 7 : AIRICE_ROOTS_STAMP ? 4 : 3;
+// ints per query of the AIRICE_SOLVE_STATS record: evaluations, secant steps, midpoints (Park::stats)
+constexpr int kStatsInts = 3;
 // evaluation-free bisection steps of the root finder per loop trip (as compare-and-select)
 constexpr int kLeanUnroll = 4;
 // table stores take an SGPR column base and a 32-bit lane byte offset (global_store saddr form):
@@ -510,13 +503,9 @@ __global__ __launch_bounds__(256) void angle_sines_kernel(DevMedium M, TableArgs
 // one segment.
 __device__ __forceinline__ void ray_solution_wave(const DevMedium& M, const IceConsts& I,
                                                   double theta, double H, bool in_ice, double* d,
-                                                  const double* tab,
-                                                  unsigned long long* ts = nullptr) {
+                                                  const double* tab) {
   const int lane = (int)(threadIdx.x & 63);
   const RowConst rc = row_const(M, I, H);
-#if AIRICE_RAY_STAMP
-  ts[1] = __builtin_amdgcn_s_memtime() + (unsigned long long)(0.0 * rc.seg.ratio);
-#endif
   const int top = rc.top, bot = I.bot;
   const bool any = rc.any != 0;
   const double A2 = M.A_air * M.A_air, A2i = M.A_ice * M.A_ice;
@@ -542,9 +531,6 @@ __device__ __forceinline__ void ray_solution_wave(const DevMedium& M, const IceC
   const double u_ice = sin_asin(I.n_ratio * vinc);
   sin_in[4] = u_ice;
   on[4] = in_ice;
-#if AIRICE_RAY_STAMP
-  ts[2] = __builtin_amdgcn_s_memtime() + (unsigned long long)(0.0 * u_ice);
-#endif
   // this lane's segment
   const int j = lane < 5 ? lane : 0;
   SegConst S = rc.seg;
@@ -576,9 +562,6 @@ __device__ __forceinline__ void ray_solution_wave(const DevMedium& M, const IceC
   double v_unused;
   const Segment sg = segment_const(S, air ? M.A_air : M.A_ice, air ? A2 : A2i, sj, air, v_unused,
                                    tab);
-#if AIRICE_RAY_STAMP
-  ts[3] = __builtin_amdgcn_s_memtime() + (unsigned long long)(0.0 * (sg.thd + sg.t + sg.geo));
-#endif
   // outputs that are functions of the chain's sines (every lane; lane 0 writes)
   const double inc = any ? k_asin(vinc) * M.r2d : 0.0;
   const double recv_ice = k_asin(sin_asin(I.iceseg.ratio * u_ice)) * M.r2d;
@@ -603,11 +586,6 @@ __device__ __forceinline__ void ray_solution_wave(const DevMedium& M, const IceC
       geo_ice += c;
     }
   }
-#if AIRICE_RAY_STAMP
-  ts[4] = __builtin_amdgcn_s_memtime() +
-          (unsigned long long)(0.0 * (thd_air + thd_ice + t_air + t_ice + geo_air + geo_ice + tS +
-                                      tP + inc + recv_ice));
-#endif
   if (lane != 0) return;
   d[0] = 0;
   d[1] = H;
@@ -636,23 +614,13 @@ __global__ __launch_bounds__(64) void scalar_ray_kernel(DevMedium M, IceConsts I
                                                         double* __restrict__ out, size_t ld,
                                                         Signal sig) {
   prefetch_kernargs<sizeof(DevMedium) + sizeof(IceConsts)>();
-  unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
-#if AIRICE_RAY_STAMP
-  // debug: shader-clock stamps (entry, row constants, sine chain, segment, sums, stores) in
-  // out[18..23], deltas from entry
-  ts[0] = __builtin_amdgcn_s_memtime();
-#endif
   const bool inl = sig.n_in >= 2;  // the inputs in the kernel arguments
   double d[18];
   ray_solution_wave(M, I, inl ? sig.in[0] : launch[0], inl ? sig.in[1] : txh[0], in_ice != 0, d,
-                    &kLogTable[0][0], ts);
+                    &kLogTable[0][0]);
   if (threadIdx.x != 0) return;
 #pragma unroll
   for (int c = 0; c < 18; ++c) out[c * ld] = d[c];
-#if AIRICE_RAY_STAMP
-  ts[5] = __builtin_amdgcn_s_memtime();
-  for (int c = 1; c < 6; ++c) out[(17 + c) * ld] = (double)(ts[c] - ts[0]);
-#endif
   signal_done(sig);
 }
 
@@ -976,49 +944,10 @@ struct SolveResult {
   double root;
   int status;
   int n_eval, n_est, n_inside;  // evaluations: all, secant search, bisection midpoints (stats)
-#if AIRICE_SCALAR_STAMP
-  int t_setup = 0, t_lean = 0;  // debug: shader clocks of the set-up and of the lean bisection runs
-  int t_pre = 0, t_post = 0;    //        loop top -> evaluation, evaluation -> loop top
-#endif
-#if AIRICE_ROOTS_STAMP == 3
-  int tb[6] = {0, 0, 0, 0, 0, 0};
-#endif
-#if AIRICE_ROOTS_STAMP == 2
-  int t_next = 0, t_eval = 0;  // debug: shader clocks in next_point and in the evaluations
-  int t_upd = 0, t_pre = 0;    //        in update, and before the loop (set-up, paired ends)
-  int t_begin = 0;             //        in the set-up (begin)
-#endif
 };
 
 enum { PH_PROBE = 0, PH_FLO = 1, PH_FHI = 2, PH_EST = 3, PH_G1 = 4, PH_G2 = 5, PH_BISECT = 6,
        PH_DONE = 7 };
-
-#if AIRICE_SORTED_STATS
-// debug build: wave-level executions of the root finder's blocks (tools/solve_blocks.py): the
-// first active lane of each execution counts it, so a block that several lanes of a wave run
-// together counts once -- the count of the wave's instruction streams through it (device code
-// only: the host form of the root finder counts nothing)
-__device__ unsigned long long g_dbg_exec[16];
-#endif
-#if AIRICE_SORTED_STATS && defined(__HIP_DEVICE_COMPILE__)
-#define DBG_EXEC(i)                                                                 \
-  do {                                                                              \
-    if ((int)(threadIdx.x & 63) == __builtin_ctzll(__ballot(1))) atomicAdd(&g_dbg_exec[i], 1ull); \
-  } while (0)
-#else
-#define DBG_EXEC(i) \
-  do {              \
-  } while (0)
-#endif
-
-// Shader clock for the debug stamp builds (0 on the host pass of the shared code).
-__host__ __device__ __forceinline__ unsigned long long dbg_clock() {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_s_memtime();
-#else
-  return 0;
-#endif
-}
 
 // Quotients and the first guess's tangent that only steer the search (the root comes from GSL's
 // bisection replay): v_rcp_f64 (~2^-24 relative) and the fast single-precision tangent on the
@@ -1089,12 +1018,6 @@ struct RootSearch {
   int phase, status, iter, est, n_eval, n_inside;
   bool root_zero;  // the failed probe reports root 0 (.cc:1500-1509)
   bool okL, okR, exact;
-#if AIRICE_SCALAR_STAMP
-  int t_lean;
-#endif
-#if AIRICE_ROOTS_STAMP == 3
-  int tb[6];  // debug: set-up stamps (tx endpoint, ice endpoint + rtop, ratio, rx, probe, total)
-#endif
 
   __host__ __device__ __forceinline__ double& dlt() { return x1; }
 
@@ -1104,14 +1027,8 @@ struct RootSearch {
   __host__ __device__ __forceinline__ void begin(const DevMedium& M, const IceConsts& I, const Geometry& g,
                                         double thR, bool exact_,
                                         const IceAirPre* pre = nullptr) {
-#if AIRICE_ROOTS_STAMP == 3
-    const unsigned long long tb0 = dbg_clock();
-#endif
     status = 0;
     exact = exact_;
-#if AIRICE_SCALAR_STAMP
-    t_lean = 0;
-#endif
     q.depth_pos = g.depth_pos;
     q.dist = g.D;
     q.top = top_layer(M, g.H);
@@ -1134,9 +1051,6 @@ struct RootSearch {
       q.iceair = air_slim(M, g.ice, n_ice);
     }
     q.tx = air_slim(M, g.H, q.n_tx);
-#if AIRICE_ROOTS_STAMP == 3
-    tb[0] = (int)(dbg_clock() + (unsigned long long)(0.0 * (q.tx.y2 + q.n_tx)) - tb0);
-#endif
     // Rx end of the top layer: the ice, or the layer's lower boundary (stop endpoint)
     const bool to_ice = q.top == q.bot;
     q.rtop = pick(to_ice, q.iceair, stop_slim(M, q.top));
@@ -1146,13 +1060,7 @@ struct RootSearch {
       q.rtop = q.tx;
       q.n_rtop = q.n_tx;
     }
-#if AIRICE_ROOTS_STAMP == 3
-    tb[1] = (int)(dbg_clock() + (unsigned long long)(0.0 * (q.rtop.y2 + q.n_rtop)) - tb0);
-#endif
     q.ratio = q.n_tx / q.n_rtop;
-#if AIRICE_ROOTS_STAMP == 3
-    tb[2] = (int)(dbg_clock() + (unsigned long long)(0.0 * q.ratio) - tb0);
-#endif
     {
       const double e = exp(M.negC_ice * g.depth_pos);
       const double y = M.A_ice + M.B_ice * e;
@@ -1160,9 +1068,6 @@ struct RootSearch {
       // argument, so it occupies no VGPRs across the loop
       q.rx = Slim{y * y, M.A_ice * y, M.negC_ice * g.depth_pos, I.ice0.invC};
     }
-#if AIRICE_ROOTS_STAMP == 3
-    tb[3] = (int)(dbg_clock() + (unsigned long long)(0.0 * q.rx.y2) - tb0);
-#endif
     lo = thR - 16;
     hi = thR;
     phase = PH_FLO;
@@ -1205,10 +1110,6 @@ struct RootSearch {
     // GSL's reported root is 0.5 (lo + hi) of the final bracket on every path (each iterate sets
     // it so, and the exact-zero exits make lo == hi), except the failed probe, which reports 0:
     // the root is formed once at the end instead of being carried through the loop
-#if AIRICE_ROOTS_STAMP == 3
-    tb[4] = (int)(dbg_clock() + (unsigned long long)(0.0 * (lo + hi)) - tb0);
-    tb[5] = phase == PH_PROBE || (status & AIRICE_SOLVE_PROBED) ? 1 : 0;
-#endif
     root_zero = probe_bad;
     f_lower = 0.0;
     f_upper = 0.0;
@@ -1310,7 +1211,6 @@ struct RootSearch {
   __host__ __device__ __forceinline__ bool next_point(const DevMedium& M, double& x) {
     const double tol = 0.000000001;
     if (phase == PH_BISECT) {
-      DBG_EXEC(1);
       // steps that need no evaluation: an exact zero at a bracket end (GSL returns that end),
       // or a midpoint inside a guard region, whose sign is the region's: lo (left) or hi
       // (right) moves to it, as gsl_root_fsolver_iterate would
@@ -1324,20 +1224,15 @@ struct RootSearch {
         return false;
       }
       if ((okL || okR) && lo > 0.0) {
-#if AIRICE_SCALAR_STAMP
-        const unsigned long long tl0 = dbg_clock();
-#endif
         // lean run (0 < lo < hi here): the root GSL reports after a step is 0.5 (lo + hi) of the
         // new bracket either way; the interval test reduces to hi - lo < tol lo
         const double gl = okL ? gL : -1.0, gr = okR ? gR : __builtin_inf();
         const double lo0 = lo, hi0 = hi;
         bool done = false;
-        DBG_EXEC(2);
         // the whole run in closed form when its midpoints are exact (airice_lean.hpp: every
         // bracket the probe did not move), the same lo, hi, steps and exit as the steps below
         LeanRun lr;
         if (lean_closed(lo, hi, iter, gL, gR, okL, okR, tol, lr)) {
-          DBG_EXEC(13);
           lo = lr.lo;
           hi = lr.hi;
           iter += lr.steps;
@@ -1348,7 +1243,6 @@ struct RootSearch {
           // select without a divergent exit per step
           bool stop = false;
           while (!stop) {
-            DBG_EXEC(3);
 #pragma unroll
             for (int u = 0; u < kLeanUnroll; ++u) {
               const double xm = (lo + hi) / 2.0;
@@ -1367,9 +1261,6 @@ struct RootSearch {
         }
         if (lo != lo0) f_lower = fL;
         if (hi != hi0) f_upper = fR;
-#if AIRICE_SCALAR_STAMP
-        t_lean += (int)(dbg_clock() - tl0) + (int)(0.0 * (lo + hi));
-#endif
         if (done) {
           phase = PH_DONE;
           return false;
@@ -1381,7 +1272,6 @@ struct RootSearch {
     } else if (phase == PH_BISECT) {
       x = (lo + hi) / 2.0;
     } else if (phase == PH_EST) {
-      DBG_EXEC(11);
       // the secant point only steers the search (the root comes from GSL's bisection replay), so
       // its quotient takes v_rcp_f64 (~2^-24 relative) instead of the IEEE division
       x = (est == 0) ? x2 : x2 - f2 * ((x2 - x1) * rcp_steer(f2 - f1));
@@ -1413,7 +1303,6 @@ struct RootSearch {
     n_inside += (phase == PH_BISECT);
     const double f = (q.dist - (thd_ice + thd_air));
     if (phase == PH_PROBE) {
-      DBG_EXEC(5);
       if ((!k_isnan(thd_air) && thd_air > 0) || lo > hi - 0.1) {
         if (hi < 90.001 && hi > 90.00) hi = 90.05;
         phase = PH_FLO;
@@ -1438,7 +1327,6 @@ struct RootSearch {
         status |= AIRICE_SOLVE_PROBED;
       }
     } else if (phase == PH_FLO) {
-      DBG_EXEC(6);
       if (!k_isfinite(f)) {
         status |= AIRICE_SOLVE_NONFINITE_END;
         phase = PH_BISECT;
@@ -1447,10 +1335,8 @@ struct RootSearch {
         phase = PH_FHI;
       }
     } else if (phase == PH_FHI) {
-      DBG_EXEC(7);
       on_fhi(M, f);
     } else if (phase == PH_EST) {
-      DBG_EXEC(8);
       if (est > 0) {
         x0 = x1;
         f0 = f1;
@@ -1477,7 +1363,7 @@ struct RootSearch {
         // [x2 - dlt, x2 + dlt].  Otherwise, and for the first search point (x1 is the bracket
         // end), both guards are evaluated (a side whose guard already lies at the root needs none).
         const bool consistent = a * b > 0.0 && fabs(a) <= 2.0 * fabs(b) && fabs(b) <= 2.0 * fabs(a);
-        if (room && est >= 2 && (AIRICE_NO_CHECK || consistent)) {
+        if (room && est >= 2 && consistent) {
           const double fm = sl > 0.0 ? -tau : tau;  // f(x2 - dlt)
           guard(x2 - dlt(), fm);
           guard(x2 + dlt(), -fm);
@@ -1491,11 +1377,9 @@ struct RootSearch {
         if (est >= 12) phase = PH_BISECT;
       }
     } else if (phase == PH_G1 || phase == PH_G2) {
-      DBG_EXEC(9);
       if (k_isfinite(f)) guard(x, f);
       phase = phase == PH_G1 ? PH_G2 : PH_BISECT;
     } else {  // PH_BISECT: gsl_root_fsolver_iterate at a midpoint between the guards
-      DBG_EXEC(10);
       if (!exact && k_isfinite(f)) guard(x, f);
       ++iter;
       bool frozen = false;
@@ -1545,34 +1429,15 @@ __host__ __device__ __forceinline__ SolveResult solve_root(const DevMedium& M, c
                                                   const Geometry& g, double thR, bool exact,
                                                   const double* tab,
                                                   const IceAirPre* pre = nullptr) {
-#if AIRICE_SCALAR_STAMP
-  const unsigned long long ts0 = dbg_clock();
-#endif
-#if AIRICE_ROOTS_STAMP == 2
-  const unsigned long long ts_entry = dbg_clock();
-#endif
   RootSearch s;
   s.begin(M, I, g, thR, exact, pre);
-#if AIRICE_ROOTS_STAMP == 2
-  const unsigned long long ts_begun = dbg_clock() + (unsigned long long)(0.0 * (s.lo + s.hi + s.q.ratio));
-#endif
   if constexpr (!WAVE) s.ends_paired(M, I, tab);
-#if AIRICE_SCALAR_STAMP
-  const int t_setup = (int)(dbg_clock() - ts0) + (int)(0.0 * (s.lo + s.hi));
-  int t_pre = 0, t_post = 0;
-  unsigned long long tq = dbg_clock();
-#endif
   // WAVE: f(lo) and f(hi), and the two guards, are independent pairs of points; the wave evaluates
   // each pair at once and keeps the second value for the next trip (the same points, the same
   // bits, two sequential evaluations fewer)
   bool have_next = false;
   double next_air = 0.0, next_ice = 0.0;
-#if AIRICE_ROOTS_STAMP == 2
-  int rs_next = 0, rs_eval = 0, rs_upd = 0;
-  const unsigned long long rs_l0 = dbg_clock() + (unsigned long long)(0.0 * (s.lo + s.hi));
-#endif
   while (s.phase != PH_DONE) {
-    DBG_EXEC(0);
     if constexpr (WAVE) {
       // one query per wave: the phase and the counters are the same on every lane; scalar copies
       // let the phase dispatch branch on SCC instead of exec masks
@@ -1581,17 +1446,8 @@ __host__ __device__ __forceinline__ SolveResult solve_root(const DevMedium& M, c
       s.iter = __builtin_amdgcn_readfirstlane(s.iter);
     }
     double x;
-#if AIRICE_ROOTS_STAMP == 2
-    const unsigned long long tn0 = dbg_clock();
-    const bool more = s.next_point(M, x);
-    const unsigned long long tn1 = dbg_clock() + (unsigned long long)(0.0 * x);
-    rs_next += (int)(tn1 - tn0);
-    if (!more) break;
-#else
     if (!s.next_point(M, x)) break;
-#endif
     // the single evaluation site: MinimizeforLaunchAngle (.cc:873-917)
-    DBG_EXEC(4);
     double thd_air, thd_ice;
     const int ph = s.phase;
     if constexpr (WAVE) {
@@ -1604,65 +1460,17 @@ __host__ __device__ __forceinline__ SolveResult solve_root(const DevMedium& M, c
         // (then always the second: PH_G1 -> PH_G2)
         const bool pair = ph == PH_FLO || ph == PH_G1;
         const double xb = ph == PH_FLO ? s.hi : s.x2 + s.dlt();
-#if AIRICE_SCALAR_STAMP
-        const unsigned long long e0 = dbg_clock();
-        t_pre += (int)(e0 - tq) + (int)(0.0 * x);
-#endif
         eval_thd_wave(M, I, s.q, x, pair ? xb : x, tab, thd_air, thd_ice, next_air, next_ice);
-#if AIRICE_SCALAR_STAMP
-        // debug: evaluation ticks in n_inside (the wave form does not count midpoints)
-        tq = dbg_clock();
-        s.n_inside += (int)(tq - e0) + (int)(0.0 * (thd_air + thd_ice));
-#endif
         have_next = pair;
       }
     } else {
-#if AIRICE_ROOTS_STAMP == 2
-      const unsigned long long te0 = dbg_clock() + (unsigned long long)(0.0 * x);
       eval_thd(M, I, s.q, x, tab, thd_air, thd_ice);
-      rs_eval += (int)(dbg_clock() + (unsigned long long)(0.0 * (thd_air + thd_ice)) - te0);
-#else
-      eval_thd(M, I, s.q, x, tab, thd_air, thd_ice);
-#endif
     }
-#if AIRICE_ROOTS_STAMP == 2
-    const unsigned long long tu0 = dbg_clock() + (unsigned long long)(0.0 * (thd_air + thd_ice));
     s.template update<!WAVE>(M, x, thd_air, thd_ice);
-    rs_upd += (int)(dbg_clock() + (unsigned long long)(0.0 * (s.lo + s.hi + s.x2)) - tu0);
-#else
-    s.template update<!WAVE>(M, x, thd_air, thd_ice);
-#endif
     // f(hi) is not wanted after all when f(lo) was not finite
     if (WAVE && ph == PH_FLO && s.phase != PH_FHI) have_next = false;
-#if AIRICE_SCALAR_STAMP
-    if constexpr (WAVE) {
-      const unsigned long long te = dbg_clock();
-      t_post += (int)(te - tq) + (int)(0.0 * (s.lo + s.hi + s.x2));
-      tq = te;
-    }
-#endif
   }
-#if AIRICE_SCALAR_STAMP
-  SolveResult sr{s.root(), s.status, s.n_eval, s.est, s.n_inside};
-  sr.t_setup = t_setup;
-  sr.t_lean = s.t_lean;
-  sr.t_pre = t_pre;
-  sr.t_post = t_post;
-  return sr;
-#else
-  SolveResult sr{s.root(), s.status, s.n_eval, s.est, s.n_inside};
-#if AIRICE_ROOTS_STAMP == 3
-  for (int i = 0; i < 6; ++i) sr.tb[i] = s.tb[i];
-#endif
-#if AIRICE_ROOTS_STAMP == 2
-  sr.t_next = rs_next;
-  sr.t_eval = rs_eval;
-  sr.t_upd = rs_upd;
-  sr.t_pre = (int)(rs_l0 - ts_entry);
-  sr.t_begin = (int)(ts_begun - ts_entry);
-#endif
-  return sr;
-#endif
+  return SolveResult{s.root(), s.status, s.n_eval, s.est, s.n_inside};
 }
 
 struct Solved {
@@ -1964,9 +1772,6 @@ template <int IN>
 __global__ __launch_bounds__(kRootsBlock, kRootsWaves) void roots_kernel(DevMedium M, IceConsts I,
                                                                          QueryArgs Q, Park park) {
   static_assert(solves_every_lane(IN), "IN_CM100 lanes are masked: use lookup_kernel");
-#if AIRICE_ROOTS_STAMP
-  const unsigned long long st0 = __builtin_amdgcn_s_memtime();
-#endif
   __shared__ int s_count[kSortBuckets + 1];
   __shared__ int s_slot[kRootsBlock];
   __shared__ double s_q[6][kRootsBlock];  // the sorted queries' geometry and straight-line angle
@@ -2017,9 +1822,6 @@ __global__ __launch_bounds__(kRootsBlock, kRootsWaves) void roots_kernel(DevMedi
   __syncthreads();
   const long long k = k0 + s_slot[threadIdx.x];
   if (k >= Q.n) return;
-#if AIRICE_ROOTS_STAMP
-  const unsigned long long st1 = __builtin_amdgcn_s_memtime() + (unsigned long long)(k & 0);
-#endif
   Geometry g;
   g.H = s_q[0][threadIdx.x];
   g.D = s_q[1][threadIdx.x];
@@ -2027,44 +1829,15 @@ __global__ __launch_bounds__(kRootsBlock, kRootsWaves) void roots_kernel(DevMedi
   g.depth = s_q[3][threadIdx.x];
   g.depth_pos = s_q[4][threadIdx.x];
   const double thR = s_q[5][threadIdx.x];
-#if AIRICE_ROOTS_STAMP
-  const unsigned long long st2 =
-      __builtin_amdgcn_s_memtime() + (unsigned long long)(0.0 * (thR + g.H + g.D + g.depth + g.ice));
-#endif
   const SolveResult r = solve_root(M, I, g, thR, park.exact != 0, &s_logtab[0][0],
                                    kIcePre ? &s_ice : nullptr);
   st_agent(park.root + k * park.stride, r.root);
   st_agent(park.status + k * park.stride, (double)r.status);
-#if AIRICE_ROOTS_STAMP
-  const unsigned long long st3 = __builtin_amdgcn_s_memtime() + (unsigned long long)(0.0 * r.root);
-  if (park.stats != nullptr) {
-#if AIRICE_ROOTS_STAMP == 3
-    park.stats[8 * k] = (int)(unsigned)st0 + 0 * (int)(st1 - st0);
-    park.stats[8 * k + 1] = (int)(st3 - st2);
-    for (int i = 0; i < 6; ++i) park.stats[8 * k + 2 + i] = r.tb[i];
-#elif AIRICE_ROOTS_STAMP == 2
-    // the search split: next_point, the evaluations and the rest (update, loop control)
-    park.stats[7 * k] = (int)(unsigned)st0 + 0 * (int)(st1 - st0);
-    park.stats[7 * k + 1] = (int)(st3 - st2);
-    park.stats[7 * k + 2] = r.t_eval;
-    park.stats[7 * k + 3] = r.t_next;
-    park.stats[7 * k + 4] = r.t_upd;
-    park.stats[7 * k + 5] = r.t_pre;
-    park.stats[7 * k + 6] = r.t_begin;
-#else
-    park.stats[4 * k] = (int)(unsigned)st0;
-    park.stats[4 * k + 1] = (int)(st1 - st0);
-    park.stats[4 * k + 2] = (int)(st2 - st0);
-    park.stats[4 * k + 3] = (int)(st3 - st0);
-#endif
-  }
-#else
   if (park.stats != nullptr) {
     park.stats[3 * k] = r.n_eval;
     park.stats[3 * k + 1] = r.n_est;
     park.stats[3 * k + 2] = r.n_inside;
   }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -2193,19 +1966,10 @@ __global__ __launch_bounds__(kSortedBlock, kRootsWaves) void roots_sorted_kernel
   const long long ks = (long long)blockIdx.x * kSortedBlock + threadIdx.x;
   static_assert(solves_every_lane(IN), "IN_CM100 lanes are masked: use lookup_kernel");
   if (ks >= *grouped) return;  // past the queries with a bucket
-  DBG_EXEC(12);
   double thR;
   const Geometry g = load_rec<IN>(M, Q, recs[ks], thR);
   const SolveResult r = solve_root(M, I, g, thR, park.exact != 0, &s_logtab[0][0]);
   sorted_park[ks] = make_double2(r.root, (double)r.status);
-#if AIRICE_SORTED_STATS
-  // debug build: evaluation counts by sorted position, i.e. in the order the waves run them
-  if (park.stats != nullptr) {
-    park.stats[3 * ks] = r.n_eval;
-    park.stats[3 * ks + 1] = r.n_est;
-    park.stats[3 * ks + 2] = r.n_inside;
-  }
-#endif
 }
 
 // Stage 1's result of query k for stage 2.
@@ -2468,9 +2232,6 @@ __global__ __launch_bounds__(64) void scalar_solve_kernel(DevMedium M, IceConsts
                                                           Park park, double* out, size_t ld,
                                                           uint8_t* flag, Signal sig) {
   prefetch_kernargs<sizeof(DevMedium) + sizeof(IceConsts)>();
-#if AIRICE_SCALAR_STAMP
-  const unsigned long long c0 = __builtin_amdgcn_s_memtime(), w0 = __builtin_amdgcn_s_memrealtime();
-#endif
   // one wave and a handful of logarithms per evaluation: the log table is read from global
   // memory (L1 / L2 after the first call) instead of being staged in LDS first
   const double* tab = &kLogTable[0][0];
@@ -2479,17 +2240,11 @@ __global__ __launch_bounds__(64) void scalar_solve_kernel(DevMedium M, IceConsts
     return;
   }
   double thR;
-#if AIRICE_SCALAR_STAMP
-  const unsigned long long c1 = __builtin_amdgcn_s_memtime();
-#endif
   const Geometry g = load_query<IN>(M, Q, 0, thR, 
                                     sig.n_in >= ((IN == IN_TRACE || (IN == IN_M && Q.d != nullptr)) ? 4 : 3)
                                         ? &sig
                                         : nullptr);
   const SolveResult r = solve_root<true>(M, I, g, thR, park.exact != 0, tab);
-#if AIRICE_SCALAR_STAMP
-  const unsigned long long c2 = __builtin_amdgcn_s_memtime();
-#endif
   // every lane runs the stage-2 body (its evaluation spread over the wave); lane 0 writes
   const WaveRoot wr{r.root, r.status, g};
   if (OUT == OUT_SOLVE_MR)
@@ -2500,20 +2255,6 @@ __global__ __launch_bounds__(64) void scalar_solve_kernel(DevMedium M, IceConsts
   if (OUT == OUT_FALLBACK) lookup_fallback_out_body<true>(M, I, Q, out, ld, flag, 0, tab, wr);
   if (OUT == OUT_TRACE) trace_out_body<true>(M, I, Q, out, 0, tab, wr);
   if (threadIdx.x != 0) return;
-#if AIRICE_SCALAR_STAMP
-  const unsigned long long c3 = __builtin_amdgcn_s_memtime(), w3 = __builtin_amdgcn_s_memrealtime();
-  out[17 * ld] = (double)(c1 - c0);
-  out[18 * ld] = (double)(c2 - c1);
-  out[19 * ld] = (double)(c3 - c2);
-  out[20 * ld] = (double)(c3 - c0);
-  out[21 * ld] = (double)(w3 - w0);
-  out[22 * ld] = (double)r.n_eval;
-  out[23 * ld] = (double)r.n_inside;
-  out[24 * ld] = (double)r.t_setup;
-  out[25 * ld] = (double)r.t_lean;
-  out[26 * ld] = (double)r.t_pre;
-  out[27 * ld] = (double)r.t_post;
-#endif
   signal_done(sig);
 }
 
@@ -2576,12 +2317,15 @@ int trace_host_one(const DevMedium& M, const IceConsts& I, const double* in, dou
   return AIRICE_OK;
 }
 
+// QueryArgs::ice of the IN_CM100 source: .cc:1309 turns IceLayerHeight into metres and .cc:1419
+// passes IceLayerHeight*100 to the minimizer fallback.
+static inline double fallback_ice_arg(double ice_cm) { return (ice_cm / 100) * 100; }
+
 // The table lookup's minimizer fallback for one flagged query (in: src, dist, depth in cm; ok and
 // flags as the lookup left them).
 int lookup_fallback_host_one(const DevMedium& M, const IceConsts& I, double ice_cm,
                              const double* in, double* out9, uint8_t* ok, const uint8_t* flags) {
-  const double ice_arg = (ice_cm / 100) * 100;  // as launch_lookup_fallback (.cc:1309, 1419)
-  const QueryArgs Q{in, in + 1, in + 2, nullptr, ice_arg, 1, flags};
+  const QueryArgs Q{in, in + 1, in + 2, nullptr, fallback_ice_arg(ice_cm), 1, flags};
   const Park park{out9 + 4, out9, 1, bisect_exact(), nullptr};
   solve_one_host_t<IN_CM100, OUT_FALLBACK>(M, I, Q, park, out9, 1, ok);
   return AIRICE_OK;
@@ -2658,7 +2402,7 @@ static int launch_roots(const DevMedium& M, const IceConsts& I, const QueryArgs&
   ws = nullptr;
   const size_t group_min = group_min_batch(IN);
   if (group_min == 0 || n < group_min ||
-      (park.stats != nullptr && !AIRICE_SORTED_STATS) || n >= (1ull << 31)) {
+      park.stats != nullptr || n >= (1ull << 31)) {
     ktimer_begin(KT_ROOTS, st);
     count_launch(LC_ROOTS);
     hipLaunchKernelGGL((roots_kernel<IN>), roots_grid(n), dim3(kRootsBlock), 0, st, M, I, Q, park);
@@ -2717,6 +2461,30 @@ struct RootsScratch {
     return AIRICE_OK;
   }
 };
+
+// The two stages of a minimizer batch on one stream: launch_roots<IN>, then between() (launch_solve's
+// statistics dump; non-zero ends the launch), then the stage-2 kernel, which out(sp) enqueues, and
+// the release of a grouped launch's scratch behind it.
+template <int IN, class Out, class Between>
+static int launch_stages(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
+                         const Park& park, hipStream_t st, Out out, Between between) {
+  SortedPark sp;
+  RootsScratch scr(st);
+  if (int rc = launch_roots<IN>(M, I, Q, park, (size_t)Q.n, st, sp, scr.ws)) return rc;
+  if (int rc = between()) return rc;
+  ktimer_begin(KT_OUT, st);
+  count_launch(LC_OUT);
+  out(sp);
+  ktimer_end(KT_OUT, st);
+  const int rc = launch_ok();
+  if (int rf = scr.release()) return rf;
+  return rc;
+}
+template <int IN, class Out>
+static int launch_stages(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
+                         const Park& park, hipStream_t st, Out out) {
+  return launch_stages<IN>(M, I, Q, park, st, out, [] { return AIRICE_OK; });
+}
 
 // Per-grid device caches of the table launch: the row constants of every Tx-height row
 // (RowConst, 104 B; rowconst_kernel) and the start-angle sine of every grid column (8 B;
@@ -2923,19 +2691,6 @@ static int angle_sines_cached(const DevMedium& M, const TableArgs& A, hipStream_
   return rc;
 }
 
-#if AIRICE_SORTED_STATS
-int debug_exec_counters(unsigned long long* out, int n, int reset) {
-  if (n > 16) n = 16;
-  if (hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg_exec), sizeof(unsigned long long) * n) != hipSuccess)
-    return AIRICE_EHIP;
-  if (reset) {
-    static const unsigned long long z[16] = {};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_dbg_exec), z, sizeof(z)) != hipSuccess) return AIRICE_EHIP;
-  }
-  return AIRICE_OK;
-}
-#endif
 
 void table_cache_stats(int out[6]) {
   std::lock_guard<std::mutex> lock(grid_cache_mutex());
@@ -2943,28 +2698,38 @@ void table_cache_stats(int out[6]) {
   angle_cache().stats(&out[3], &out[4], &out[5]);
 }
 
+// Rows a block's kTableBlock rays can touch, for the LDS row constants.
+static inline int table_rows_per_block(int angle_steps) {
+  return std::min(kTableBlock, (kTableBlock - 1) / angle_steps + 2);
+}
+
+// The grid's part of a table launch's arguments; the launcher adds row0, n, half and the caches
+// (rc, vs).  Written in place over zeroed bytes, padding included: launch_table_multi compares
+// the packed arguments of its antenna sets bytewise.
+static void table_args(TableArgs& A, const airice_grid& g, size_t ld, int rows_per_block) {
+  std::memset(&A, 0, sizeof(A));
+  A.start_h = g.start_height;
+  A.stop_h = g.stop_height;
+  A.step_h = g.height_step;
+  A.start_a = g.start_angle;
+  A.stop_a = g.stop_angle;
+  A.step_a = g.angle_step;
+  A.inv_asteps = 1.0 / (double)g.angle_steps;
+  A.hsteps = g.height_steps;
+  A.asteps = g.angle_steps;
+  A.in_ice = g.in_ice;
+  A.rows_per_block = rows_per_block;
+  A.ld = ld;
+}
+
 int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, int row_begin,
                  int row_count, float* d_table, double* d_full, size_t ld, hipStream_t st) {
   if (row_count <= 0 || g->angle_steps <= 0) return AIRICE_OK;
   TableArgs A;
-  A.start_h = g->start_height;
-  A.stop_h = g->stop_height;
-  A.step_h = g->height_step;
-  A.start_a = g->start_angle;
-  A.stop_a = g->stop_angle;
-  A.step_a = g->angle_step;
-  A.hsteps = g->height_steps;
-  A.asteps = g->angle_steps;
-  A.in_ice = g->in_ice;
-  A.ld = ld;
-  A.inv_asteps = 1.0 / (double)g->angle_steps;
-  // rows a 256-ray set can touch, for the LDS row constants
-  A.rows_per_block = std::min(kTableBlock, (kTableBlock - 1) / g->angle_steps + 2);
-  A.rc = nullptr;
+  table_args(A, *g, ld, table_rows_per_block(g->angle_steps));
   std::unique_lock<std::mutex> rs_lock(grid_cache_mutex());  // held until the launches are enqueued
   const bool fill_first = (long long)row_count * g->angle_steps >= kFillFirstRays;
   if (int rc = row_consts_cached(M, I, A, st, fill_first, &A.rc)) return rc;
-  A.vs = nullptr;
   if (int rc = angle_sines_cached(M, A, st, fill_first, &A.vs)) return rc;
   static const char* trace_path = getenv("AIRICE_TABLE_TRACE");
   // ray indices are 32-bit inside a launch: grids of kMaxLaunchRays or more go in row slabs
@@ -2984,18 +2749,11 @@ int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, i
       ktimer_begin(KT_TABLE, st);
       count_launch(LC_TABLE);
       const bool sc1 = A.n < kAgentStoreRays;
-      if (M.A_air == 1.0 && sc1)
-        hipLaunchKernelGGL((table_kernel<false, true, true>), dim3(blocks), dim3(kTableBlock), lds,
-                           st, M, I, A, tab, full, nullptr);
-      else if (M.A_air == 1.0)
-        hipLaunchKernelGGL((table_kernel<false, true, false>), dim3(blocks), dim3(kTableBlock), lds,
-                           st, M, I, A, tab, full, nullptr);
-      else if (sc1)
-        hipLaunchKernelGGL((table_kernel<false, false, true>), dim3(blocks), dim3(kTableBlock), lds,
-                           st, M, I, A, tab, full, nullptr);
-      else
-        hipLaunchKernelGGL((table_kernel<false, false, false>), dim3(blocks), dim3(kTableBlock), lds,
-                           st, M, I, A, tab, full, nullptr);
+      auto kern = M.A_air == 1.0
+                      ? (sc1 ? table_kernel<false, true, true> : table_kernel<false, true, false>)
+                      : (sc1 ? table_kernel<false, false, true> : table_kernel<false, false, false>);
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(kTableBlock), lds, st, M, I, A, tab, full,
+                         nullptr);
       ktimer_end(KT_TABLE, st);
       if (hipGetLastError() != hipSuccess) return AIRICE_EHIP;
       continue;
@@ -3039,30 +2797,15 @@ int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_gri
   const int rpb = [&] {
     int r = 2;
     for (int a = 0; a < n; ++a)
-      r = std::max(r, std::min(kTableBlock, (kTableBlock - 1) / grids[a].angle_steps + 2));
+      r = std::max(r, table_rows_per_block(grids[a].angle_steps));
     return r;
   }();
   for (int a = 0; a < n; ++a) {
     const airice_grid* g = &grids[a];
     TableArgs& A = Ah[a];
-    std::memset(&A, 0, sizeof(A));
-    A.start_h = g->start_height;
-    A.stop_h = g->stop_height;
-    A.step_h = g->height_step;
-    A.start_a = g->start_angle;
-    A.stop_a = g->stop_angle;
-    A.step_a = g->angle_step;
-    A.hsteps = g->height_steps;
-    A.asteps = g->angle_steps;
-    A.in_ice = g->in_ice;
-    A.ld = lds[a];
-    A.inv_asteps = 1.0 / (double)g->angle_steps;
-    A.rows_per_block = rpb;
-    A.row0 = 0;
-    A.rc = nullptr;
+    table_args(A, *g, lds[a], rpb);
     const bool fill_first = (long long)g->table_rows * g->angle_steps >= kFillFirstRays;
     if (int rc = row_consts_cached(M, Ih[a], A, st, fill_first, &A.rc)) return rc;
-    A.vs = nullptr;
     if (int rc = angle_sines_cached(M, A, st, fill_first, &A.vs)) return rc;
     const long long rays = (long long)g->table_rows * g->angle_steps;
     if (rays >= kMaxLaunchRays - 2 * kTableBlock || lds[a] < (size_t)rays) {
@@ -3203,10 +2946,8 @@ int launch_solve(const DevMedium& M, const IceConsts& I, int variant, const doub
                          Q, park, out, ld, status, sig);
     return launch_ok();
   }
-  SortedPark sp;
-  RootsScratch scr(st);
-  if (int rc = launch_roots<IN_M>(M, I, Q, park, n, st, sp, scr.ws)) return rc;
-  if (park.stats != nullptr) {  // debug: append the per-query counts (synchronous)
+  auto dump_stats = [&] {  // debug: append the per-query counts (synchronous)
+    if (park.stats == nullptr) return AIRICE_OK;
     std::vector<int> h(kStatsInts * n);
     if (hipStreamSynchronize(st) != hipSuccess ||
         hipMemcpy(h.data(), park.stats, sizeof(int) * kStatsInts * n, hipMemcpyDeviceToHost) != hipSuccess)
@@ -3216,19 +2957,16 @@ int launch_solve(const DevMedium& M, const IceConsts& I, int variant, const doub
       fwrite(h.data(), sizeof(int), kStatsInts * n, f);
       fclose(f);
     }
-  }
-  ktimer_begin(KT_OUT, st);
-  count_launch(LC_OUT);
-  if (variant == AIRICE_VARIANT_MULTIRAY)
-    hipLaunchKernelGGL(solve_out_kernel<AIRICE_VARIANT_MULTIRAY>, grid, block, 0, st, M, I, Q, out,
-                       ld, status, sp);
-  else
-    hipLaunchKernelGGL(solve_out_kernel<AIRICE_VARIANT_PYWRAPPER>, grid, block, 0, st, M, I, Q,
-                       out, ld, status, sp);
-  ktimer_end(KT_OUT, st);
-  const int rc = launch_ok();
-  if (int rf = scr.release()) return rf;
-  return rc;
+    return AIRICE_OK;
+  };
+  auto stage2 = variant == AIRICE_VARIANT_MULTIRAY ? solve_out_kernel<AIRICE_VARIANT_MULTIRAY>
+                                                   : solve_out_kernel<AIRICE_VARIANT_PYWRAPPER>;
+  return launch_stages<IN_M>(
+      M, I, Q, park, st,
+      [&](const SortedPark& sp) {
+        hipLaunchKernelGGL(stage2, grid, block, 0, st, M, I, Q, out, ld, status, sp);
+      },
+      dump_stats);
 }
 
 int launch_hdtip(const DevMedium& M, const IceConsts& I, const double* src, const double* dist,
@@ -3244,16 +2982,9 @@ int launch_hdtip(const DevMedium& M, const IceConsts& I, const double* src, cons
                        park, out, ld, ok, take_scalar_signal());
     return launch_ok();
   }
-  SortedPark sp;
-  RootsScratch scr(st);
-  if (int rc = launch_roots<IN_CM>(M, I, Q, park, n, st, sp, scr.ws)) return rc;
-  ktimer_begin(KT_OUT, st);
-  count_launch(LC_OUT);
-  hipLaunchKernelGGL(hdtip_out_kernel, grid, block, 0, st, M, I, Q, out, ld, ok, sp);
-  ktimer_end(KT_OUT, st);
-  const int rc = launch_ok();
-  if (int rf = scr.release()) return rf;
-  return rc;
+  return launch_stages<IN_CM>(M, I, Q, park, st, [&](const SortedPark& sp) {
+    hipLaunchKernelGGL(hdtip_out_kernel, grid, block, 0, st, M, I, Q, out, ld, ok, sp);
+  });
 }
 
 // The table lookup's minimizer fallback for one query (the one-query device call; a batch solves
@@ -3263,9 +2994,7 @@ int launch_lookup_fallback(const DevMedium& M, const IceConsts& I, const double*
                            double* out, size_t ld, uint8_t* ok, const uint8_t* flags,
                            hipStream_t st) {
   if (n == 0) return AIRICE_OK;
-  // .cc:1309 turns IceLayerHeight into metres; .cc:1419 passes IceLayerHeight*100
-  const double ice_arg = (ice_cm / 100) * 100;
-  const QueryArgs Q{src, dist, depth, nullptr, ice_arg, (long long)n, flags};
+  const QueryArgs Q{src, dist, depth, nullptr, fallback_ice_arg(ice_cm), (long long)n, flags};
   const Park park{out + 4 * ld, out, 1, bisect_exact(), nullptr};
   if (n != 1) {
     set_error("launch_lookup_fallback: one query (batches solve their fallback in lookup_kernel)");
@@ -3317,8 +3046,7 @@ int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_ta
                   size_t n, double* out, size_t ld, uint8_t* ok, uint8_t* flags, hipStream_t st) {
   if (n == 0) return AIRICE_OK;
   const LkTable T = lk_table(t);
-  const double ice_arg = (ice_cm / 100) * 100;  // .cc:1309 in metres, .cc:1419 passes it x100
-  const QueryArgs Q{src, dist, depth, nullptr, ice_arg, (long long)n, flags};
+  const QueryArgs Q{src, dist, depth, nullptr, fallback_ice_arg(ice_cm), (long long)n, flags};
   const unsigned grid = (unsigned)((n + kLkBlock - 1) / kLkBlock);
   ktimer_begin(KT_LOOKUP, st);
   count_launch(LC_LOOKUP);
@@ -3340,16 +3068,9 @@ int launch_trace(const DevMedium& M, const IceConsts& I, const double* depth, co
                        park, out10, 0, nullptr, take_scalar_signal());
     return launch_ok();
   }
-  SortedPark sp;
-  RootsScratch scr(st);
-  if (int rc = launch_roots<IN_TRACE>(M, I, Q, park, n, st, sp, scr.ws)) return rc;
-  ktimer_begin(KT_OUT, st);
-  count_launch(LC_OUT);
-  hipLaunchKernelGGL(trace_out_kernel, grid, block, 0, st, M, I, Q, out10, sp);
-  ktimer_end(KT_OUT, st);
-  const int rc = launch_ok();
-  if (int rf = scr.release()) return rf;
-  return rc;
+  return launch_stages<IN_TRACE>(M, I, Q, park, st, [&](const SortedPark& sp) {
+    hipLaunchKernelGGL(trace_out_kernel, grid, block, 0, st, M, I, Q, out10, sp);
+  });
 }
 
 }  // namespace airice

@@ -7,7 +7,7 @@
 // (f has f(lo)'s sign there: lo moves) or xm >= gr (hi moves) -- until a midpoint falls strictly
 // between the guards (it must be evaluated) or the driver stops (interval test, max_iter).  Run
 // step by step that is ~25 compare-and-select steps per solve, a fifth of the root finder's VALU
-// issue (tools/solve_blocks.py).
+// issue.
 //
 // When every midpoint the run can form is exact -- the bracket width w = hi - lo a power of two,
 // the finest spacing w 2^-R (R = 40 - iter steps left) no finer than hi's ulp, lo on hi's ulp grid:
