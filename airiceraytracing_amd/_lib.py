@@ -157,7 +157,8 @@ EXPORTED_SYMBOLS = (
     "airice_table_launch_multi",
     "airice_table_host", "airice_rays_launch", "airice_rays_host", "airice_scalar_mode", "airice_solve_launch", "airice_solve_host",
     "airice_hdtip_launch", "airice_table_lookup_launch", "airice_lookup_pack", "airice_lookup_pack_floats", "airice_single_ray_plan",
-    "airice_single_ray_launch", "airice_single_ray_host", "airice_trace_ice_to_air_launch",
+    "airice_single_ray_launch", "airice_single_ray_host", "airice_ray_paths_plan",
+    "airice_ray_paths_launch", "airice_ray_paths_host", "airice_trace_ice_to_air_launch",
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
     "airice_rtf_eval_variant", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
@@ -226,6 +227,9 @@ def lib() -> ctypes.CDLL:
         "airice_single_ray_plan": ([M, D, D, D, D, ctypes.POINTER(SingleRayInfo)], I),
         "airice_single_ray_launch": ([M, D, D, D, D, P, P, P, S, P], I),
         "airice_single_ray_host": ([M, D, D, D, D, P, P, P, S], I),
+        "airice_ray_paths_plan": ([M, D, D, P, S, P, ctypes.POINTER(S)], I),
+        "airice_ray_paths_launch": ([M, D, D, P, P, S, P, P, S, P, S, P, P, S, P], I),
+        "airice_ray_paths_host": ([M, D, D, P, P, S, P, P, S, P, P, S], I),
         "airice_rtf_outputs": ([I, I], I),
         "airice_rtf_eval": ([M, I, P, S, P, S], I),
         "airice_rtf_eval_variant": ([M, I, I, P, S, P, S], I),

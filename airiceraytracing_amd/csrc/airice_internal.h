@@ -65,6 +65,15 @@ int plan_single_ray(const airice_medium* m, double depth, double launch, double 
 int launch_single_ray(const DevMedium& M, const airice_medium* m, double depth, double launch,
                       double txh, double ice, double* d_work, double* d_x, double* d_z,
                       size_t cap, hipStream_t st);
+// The batch of the same sampler: n rays sharing depth and ice, per-ray Tx height (host) and
+// launch angle (device).  The plan is host-only; the launch uploads the per-ray plans and the
+// tile list into d_work (work_bytes from the plan) and makes no allocation.
+int plan_ray_paths(const airice_medium* m, double depth, double ice, const double* txh, size_t n,
+                   int64_t* offsets, size_t* work_bytes);
+int launch_ray_paths(const DevMedium& M, const airice_medium* m, double depth, double ice,
+                     const double* d_launch, const double* txh, size_t n, const int64_t* offsets,
+                     void* d_work, size_t work_bytes, double* d_summary, size_t ld, double* d_x,
+                     double* d_z, size_t cap, hipStream_t st);
 // RayTracingFunctions:: scalar layer (airice_rtf.hip): one call, one lane, d_out >= outputs
 int rtf_outputs(int op, int max_layers);
 int rtf_host(const DevMedium& M, int op, const double* args, size_t n_args, double* out);
@@ -131,7 +140,16 @@ int lookup_fallback_one(const airice_medium* m, double src_cm, double dist_cm, d
 
 // Kernel timing for the bench (airice_kernel_timing): when enabled, launches of the kernels
 // below are bracketed by a hipEvent pair on their stream.  Off by default: one relaxed load.
-enum KTimerId { KT_TABLE = 0, KT_ROOTS, KT_GROUP, KT_OUT, KT_LOOKUP, KT_COUNT };
+enum KTimerId {
+  KT_TABLE = 0,
+  KT_ROOTS,
+  KT_GROUP,
+  KT_OUT,
+  KT_LOOKUP,
+  KT_RAY_CONSTS,
+  KT_RAY_PATHS,
+  KT_COUNT
+};
 extern std::atomic<bool> g_ktimer_on;
 void ktimer_record(int id, bool begin, hipStream_t st);
 inline void ktimer_begin(int id, hipStream_t st) {
@@ -154,6 +172,8 @@ enum LaunchId {
   LC_RTF,           // rtf_kernel (ray layer, GSL-Brent search)
   LC_SINGLE_RAY,    // single_ray_kernel
   LC_PATH,          // path_kernel
+  LC_RAY_CONSTS,    // ray_consts_kernel
+  LC_RAY_PATHS,     // ray_paths_kernel
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

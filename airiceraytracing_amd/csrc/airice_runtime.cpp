@@ -225,14 +225,16 @@ struct KtPair {
 };
 static std::vector<KtPair> g_kt_done[KT_COUNT];   // closed pairs
 static KtPair g_kt_open[KT_COUNT];                // pair whose end is pending
-static const char* const kKtNames[KT_COUNT] = {"table_kernel", "roots_kernel", "group_passes",
-                                               "out_kernel", "lookup_kernel"};
+static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kernel",
+                                               "group_passes",      "out_kernel",
+                                               "lookup_kernel",     "ray_consts_kernel",
+                                               "ray_paths_kernel"};
 
 std::atomic<long long> g_launches[LC_COUNT];
 static const char* const kLcNames[LC_COUNT] = {
     "table_kernel",        "rays_kernel",  "scalar_ray_kernel", "roots_kernel",
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
-    "single_ray_kernel",   "path_kernel"};
+    "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel"};
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
 // them from a child process).
@@ -930,6 +932,84 @@ int airice_single_ray_host(const airice_medium* m, double antenna_depth_m, doubl
     }
   }
   return rc;
+}
+
+int airice_ray_paths_plan(const airice_medium* m, double antenna_depth_m, double ice_m,
+                          const double* txh_m, size_t n, int64_t* offsets, size_t* work_bytes) {
+  if (m == nullptr || offsets == nullptr || (n > 0 && txh_m == nullptr)) {
+    set_error("null argument");
+    return AIRICE_EINVAL;
+  }
+  return plan_ray_paths(m, antenna_depth_m, ice_m, txh_m, n, offsets, work_bytes);
+}
+
+int airice_ray_paths_launch(const airice_medium* m, double antenna_depth_m, double ice_m,
+                            const double* d_launch_deg, const double* txh_m, size_t n,
+                            const int64_t* offsets, void* d_work, size_t work_bytes,
+                            double* d_summary, size_t ld, double* d_x, double* d_z, size_t cap,
+                            void* stream) {
+  if (n == 0) return AIRICE_OK;
+  if (m == nullptr || d_launch_deg == nullptr || txh_m == nullptr || offsets == nullptr ||
+      d_work == nullptr || d_summary == nullptr || ((d_x == nullptr) != (d_z == nullptr))) {
+    set_error("ray paths: null argument (d_x/d_z both or neither)");
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("ray paths: summary stride %zu is less than %zu rays", ld, n);
+    return AIRICE_EINVAL;
+  }
+  DevMedium M;
+  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);  // RayTracingFunctions pi (.h:26)
+  if (rc) return rc;
+  rc = launch_ray_paths(M, m, antenna_depth_m, ice_m, d_launch_deg, txh_m, n, offsets, d_work,
+                        work_bytes, d_summary, ld, d_x, d_z, cap, (hipStream_t)stream);
+  if (rc == AIRICE_EHIP) set_error("ray paths launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
+
+int airice_ray_paths_host(const airice_medium* m, double antenna_depth_m, double ice_m,
+                          const double* launch_deg, const double* txh_m, size_t n,
+                          const int64_t* offsets, double* summary, size_t ld, double* x, double* z,
+                          size_t cap) {
+  if (n == 0) return AIRICE_OK;
+  if (m == nullptr || launch_deg == nullptr || txh_m == nullptr || offsets == nullptr ||
+      summary == nullptr || ((x == nullptr) != (z == nullptr))) {
+    set_error("ray paths: null argument (x/z both or neither)");
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("ray paths: summary stride %zu is less than %zu rays", ld, n);
+    return AIRICE_EINVAL;
+  }
+  std::vector<int64_t> planned(n + 1);
+  size_t work_bytes = 0;
+  int rc = plan_ray_paths(m, antenna_depth_m, ice_m, txh_m, n, planned.data(), &work_bytes);
+  if (rc) return rc;
+  const bool path = x != nullptr;
+  const size_t total = path ? (size_t)planned[n] : 0;
+  if (path && total > cap) {
+    set_error("ray paths: %zu path samples exceed capacity %zu", total, cap);
+    return AIRICE_EINVAL;
+  }
+  DevBuffer work, vals;  // vals: launch angles, summary columns, x, z
+  HIP_TRY(work.alloc(work_bytes));
+  HIP_TRY(vals.alloc(sizeof(double) * (n * (1 + AIRICE_SINGLE_RAY_FIELDS) + 2 * total)));
+  double* d_launch = static_cast<double*>(vals.p);
+  double* d_sum = d_launch + n;
+  double* dx = path ? d_sum + n * AIRICE_SINGLE_RAY_FIELDS : nullptr;
+  double* dz = path ? dx + total : nullptr;
+  HIP_TRY(hipMemcpy(d_launch, launch_deg, sizeof(double) * n, hipMemcpyHostToDevice));
+  rc = airice_ray_paths_launch(m, antenna_depth_m, ice_m, d_launch, txh_m, n, offsets, work.p,
+                               work_bytes, d_sum, n, dx, dz, total, nullptr);
+  if (rc) return rc;
+  for (int f = 0; f < AIRICE_SINGLE_RAY_FIELDS; ++f)
+    HIP_TRY(hipMemcpy(summary + (size_t)f * ld, d_sum + (size_t)f * n, sizeof(double) * n,
+                      hipMemcpyDeviceToHost));
+  if (total > 0) {
+    HIP_TRY(hipMemcpy(x, dx, sizeof(double) * total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(z, dz, sizeof(double) * total, hipMemcpyDeviceToHost));
+  }
+  return AIRICE_OK;
 }
 
 int airice_trace_ice_to_air_launch(const airice_medium* m, const double* d_depth,

@@ -258,6 +258,84 @@ class AirIceSolver:
               "airice_single_ray_host")
         return summary, x, z, info
 
+    # ------------------------------------------------------------------ ray paths, batched
+    def _ray_paths_plan(self, txh, ice: float, depth: float):
+        h = np.ascontiguousarray(txh, dtype=np.float64).ravel()
+        offsets = np.zeros(h.size + 1, dtype=np.int64)
+        work = ctypes.c_size_t(0)
+        check(lib().airice_ray_paths_plan(ctypes.byref(self.medium), depth, ice, ptr(h), h.size,
+                                          ptr(offsets), ctypes.byref(work)),
+              "airice_ray_paths_plan")
+        return h, offsets, int(work.value)
+
+    def ray_paths_plan(self, txh, ice: float, depth: float) -> np.ndarray:
+        """airice_ray_paths_plan (host only): the int64 sample offsets of a batch of rays with Tx
+        heights ``txh`` that share ``ice`` and the antenna ``depth`` (positive in ice); ray i owns
+        samples [offsets[i], offsets[i+1]).  The counts do not depend on the launch angles."""
+        return self._ray_paths_plan(txh, ice, depth)[1]
+
+    def ray_paths_work_bytes(self, txh, ice: float, depth: float) -> int:
+        """Bytes of the device workspace ``ray_paths_device`` needs for this batch."""
+        return self._ray_paths_plan(txh, ice, depth)[2]
+
+    def ray_paths_device(self, launch_deg, txh, ice: float, depth: float, offsets, summary, x, z,
+                         work=None, stream=None, ld: int | None = None):
+        """airice_ray_paths_launch: ``launch_deg`` (n float64), ``summary`` (6 x n float64) and
+        ``x`` / ``z`` (>= offsets[n] float64 each, or both None for the summaries alone) are
+        device tensors; ``txh`` and ``offsets`` (from ``ray_paths_plan``) stay on the host.
+        ``work`` is a device byte tensor of ``ray_paths_work_bytes``; without one it is allocated
+        here.  Stream-ordered; returns the workspace, which must outlive the launch."""
+        import torch
+        h = np.ascontiguousarray(txh, dtype=np.float64).ravel()
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = h.size
+        if off.size != n + 1 or int(launch_deg.numel()) != n:
+            raise ValueError(f"ray_paths_device: {n} Tx heights, {int(launch_deg.numel())} launch "
+                             f"angles, {off.size} offsets")
+        if (x is None) != (z is None):
+            raise ValueError("ray_paths_device: x and z are given together or not at all")
+        if work is None:
+            work = torch.empty(max(self.ray_paths_work_bytes(h, ice, depth), 16),
+                               dtype=torch.uint8, device=summary.device)
+        cap = 0 if x is None else min(int(x.numel()), int(z.numel()))
+        check(lib().airice_ray_paths_launch(ctypes.byref(self.medium), depth, ice, ptr(launch_deg),
+                                            ptr(h), n, ptr(off), ptr(work), int(work.numel()),
+                                            ptr(summary), n if ld is None else ld, ptr(x), ptr(z),
+                                            cap, _stream_handle(stream)),
+              "airice_ray_paths_launch")
+        return work
+
+    def ray_paths_host(self, launch_deg, txh, ice: float, depth: float, path: bool = True):
+        """airice_ray_paths_host: the paths of n rays (numpy in, numpy out).  Returns
+        (summary (6, n), offsets, x, z): the ``single_ray_host`` summary of every ray as columns
+        and the concatenated RayPathinAirnIce.txt samples, ray i in [offsets[i], offsets[i+1]);
+        x and z are empty without ``path``."""
+        a = np.ascontiguousarray(launch_deg, dtype=np.float64).ravel()
+        h = np.ascontiguousarray(np.broadcast_to(txh, a.shape), dtype=np.float64).ravel()
+        _, offsets, _ = self._ray_paths_plan(h, ice, depth)
+        n = a.size
+        total = int(offsets[n]) if path else 0
+        summary = np.empty((_lib.SINGLE_RAY_FIELDS, n))
+        x = np.empty(total)
+        z = np.empty(total)
+        check(lib().airice_ray_paths_host(ctypes.byref(self.medium), depth, ice, ptr(a), ptr(h), n,
+                                          ptr(offsets), ptr(summary), max(n, 1),
+                                          ptr(x) if path else None, ptr(z) if path else None,
+                                          total), "airice_ray_paths_host")
+        return summary, offsets, x, z
+
+    def paths_between(self, txh, dist, depth: float, ice: float):
+        """The DrawShowerRays composition (DrawShowerRays.C:483-519): solve every (Tx height,
+        horizontal distance) pair against one antenna ``depth`` m below the ice surface
+        (``solve_host``, MultiRayAirIceRefraction numerics), then sample the path of every solved
+        launch angle (slot 10, LaunchAngleAir) in one batch.  Returns (summary, offsets, x, z,
+        status): ``ray_paths_host``'s outputs and the solve's AIRICE_SOLVE_* status bytes."""
+        h = np.ascontiguousarray(txh, dtype=np.float64).ravel()
+        d = np.ascontiguousarray(np.broadcast_to(dist, h.shape), dtype=np.float64).ravel()
+        sol, status = self.solve_host(h, d, np.full(h.shape, -float(depth)), ice,
+                                      variant=VARIANT_MULTIRAY)
+        return (*self.ray_paths_host(sol[10], h, ice, float(depth)), status)
+
     # ------------------------------------------------------------------ pythonwrapper
     def trace_ice_to_air_device(self, depth, ice, txh, dist, out10, stream=None) -> None:
         n = int(depth.numel())

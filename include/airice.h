@@ -287,6 +287,42 @@ int airice_single_ray_host(const airice_medium *m, double antenna_depth_m, doubl
                            double txh_m, double ice_m, double *summary, double *x, double *z,
                            size_t cap);
 
+/* --- ray paths of many rays in one launch (the per-point loop of DrawShowerRays.C:483-519) --- */
+/* n rays that share the ice height and the antenna depth (positive in ice), each with its own
+ * launch angle and Tx height; ray i is exactly what airice_single_ray_* gives for
+ * (antenna_depth_m, launch_deg[i], txh_m[i], ice_m): the same six summary values, the same
+ * n_air + n_ice samples in RayPathinAirnIce.txt order, the same bits (both paths run the same
+ * device functions).
+ *
+ * Plan (host only, no GPU needed): offsets[0..n], offsets[0] = 0; ray i owns samples
+ * [offsets[i], offsets[i+1]) of x and z.  The count depends on (txh, ice, depth) only, not on the
+ * launch angle.  *work_bytes (nullable): the size of the launch's workspace.  A ray that
+ * airice_single_ray_plan rejects fails the batch with AIRICE_EINVAL; airice_last_error() names
+ * its index. */
+int airice_ray_paths_plan(const airice_medium *m, double antenna_depth_m, double ice_m,
+                          const double *txh_m /* host */, size_t n, int64_t *offsets /* host, n+1 */,
+                          size_t *work_bytes);
+/* Stream-ordered, no device allocation: two kernels (ray_consts_kernel: one lane per ray;
+ * ray_paths_kernel: one lane per sample of the whole batch) after the upload of the per-ray plans
+ * into d_work.  d_launch_deg: n device doubles (for instance column 10, LaunchAngleAir, of an
+ * airice_solve_launch output); txh_m and offsets: host, as given to / filled by the plan (checked
+ * against it); d_work: work_bytes device bytes, 16-byte aligned; d_summary: the six
+ * airice_single_ray summary values as double columns, value f of ray i at d_summary[f*ld + i];
+ * d_x / d_z (nullable together: summaries only): cap >= offsets[n] doubles each.  A cap or
+ * work_bytes that is too small is AIRICE_EINVAL and nothing is launched; n == 0 is AIRICE_OK and
+ * nothing is launched. */
+int airice_ray_paths_launch(const airice_medium *m, double antenna_depth_m, double ice_m,
+                            const double *d_launch_deg, const double *txh_m, size_t n,
+                            const int64_t *offsets, void *d_work, size_t work_bytes,
+                            double *d_summary, size_t ld, double *d_x, double *d_z, size_t cap,
+                            void *stream);
+/* The same with every array on the host (summary: 6 columns of stride ld; x / z nullable
+ * together): copies, launches and synchronises. */
+int airice_ray_paths_host(const airice_medium *m, double antenna_depth_m, double ice_m,
+                          const double *launch_deg, const double *txh_m, size_t n,
+                          const int64_t *offsets, double *summary, size_t ld, double *x, double *z,
+                          size_t cap);
+
 /* pythonwrapper TraceIceToAir, batched: per-query (depth, ice, txh, dist) metres ->
  * ArrayParameters[10] rows (TraceIceToAir.C:46-68), row-major n x 10. */
 int airice_trace_ice_to_air_launch(const airice_medium *m, const double *d_depth,
@@ -414,7 +450,8 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * of a timed kernel is bracketed by a hipEvent pair on its own stream.  Names:
  * "table_kernel", "roots_kernel" (roots_kernel / roots_sorted_kernel, the minimizer's root
  * finder), "group_passes" (the batch-wide grouping passes), "out_kernel" (solve_out /
- * hdtip_out / trace_out), "lookup_kernel".  airice_kernel_time waits for the recorded pairs
+ * hdtip_out / trace_out), "lookup_kernel", "ray_consts_kernel" and "ray_paths_kernel" (the two
+ * kernels of airice_ray_paths_launch).  airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
 int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, int reset);
@@ -424,7 +461,8 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * device path it checks really ran.  Names: "table_kernel", "rays_kernel", "scalar_ray_kernel",
  * "roots_kernel" (roots_kernel / roots_sorted_kernel), "scalar_solve_kernel" (the one-query
  * minimizer entry points in AIRICE_SCALAR_DEVICE mode), "out_kernel", "lookup_kernel",
- * "rtf_kernel" (ray layer and the GSL-Brent search), "single_ray_kernel", "path_kernel".
+ * "rtf_kernel" (ray layer and the GSL-Brent search), "single_ray_kernel", "path_kernel",
+ * "ray_consts_kernel", "ray_paths_kernel" (airice_ray_paths_launch).
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
