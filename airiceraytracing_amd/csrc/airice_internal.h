@@ -30,7 +30,7 @@ int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, co
                 int in_ice, size_t n, double* out, size_t ld, hipStream_t st);
 void rays_host(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
                int in_ice, size_t n, double* out, size_t ld);
-// one query of the minimizer entry points on the host (airice_kernels.hip)
+// one query of the minimizer entry points on the host (airice_kernels.hip: solve_one_host_t)
 int solve_host_one(const DevMedium& M, const IceConsts& I, int variant, const double* in,
                    bool has_thr, double* out, uint8_t* status);
 int hdtip_host_one(const DevMedium& M, const IceConsts& I, double ice_cm, const double* in,
@@ -55,10 +55,10 @@ int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_ta
                   const double* src, const double* dist, const double* depth, double ice_cm,
                   size_t n, double* out, size_t ld, uint8_t* ok, uint8_t* flags, hipStream_t st);
 int launch_lookup_pack(const airice_lookup_table* t, float* entries, hipStream_t st);
+// the lookup's fallback for one query on the device (batches solve theirs in lookup_kernel)
 int launch_lookup_fallback(const DevMedium& M, const IceConsts& I, const double* src,
-                           const double* dist, const double* depth, double ice_cm, size_t n,
-                           double* out, size_t ld, uint8_t* ok, const uint8_t* flags,
-                           hipStream_t st);
+                           const double* dist, const double* depth, double ice_cm, double* out,
+                           size_t ld, uint8_t* ok, const uint8_t* flags, hipStream_t st);
 // SingleRayAirIceRefraction (airice_path.hip).  d_work: AIRICE_SINGLE_RAY_WORK doubles.
 int plan_single_ray(const airice_medium* m, double depth, double launch, double txh, double ice,
                     airice_single_ray_info* info);
@@ -83,12 +83,6 @@ int set_scalar_mode(int mode);
 int folded_medium(const airice_medium* m, int variant, const DevMedium** out);
 int folded_ice(const airice_medium* m, int variant, double ice_h, double rx_depth,
                const DevMedium** M, const IceConsts** I);
-// one query of a minimizer entry point on the host, from an airice_medium (folds cached)
-int solve_query_host(const airice_medium* m, int variant, double ice_h, const double* in,
-                     bool has_thr, double* out, uint8_t* status);
-int hdtip_query_host(const airice_medium* m, double ice_cm, const double* in, double* out9,
-                     uint8_t* ok);
-int trace_query_host(const airice_medium* m, const double* in, double* out10);
 int launch_rtf(const DevMedium& M, int op, const double* args, size_t n_args, double* d_out,
                hipStream_t st);
 int launch_trace(const DevMedium& M, const IceConsts& I, const double* depth, const double* ice,
@@ -133,8 +127,19 @@ class ScalarCall {
 };
 // The armed signal of this thread (cleared by taking it); Signal{} when none is armed.
 Signal take_scalar_signal();
-// The table lookup's minimizer fallback for one query that lk_query flagged one-sided
-// (.cc:1418-1420), on the device through the scalar slot: out9 / *ok as the batch lookup.
+// One query of a minimizer entry point, from an airice_medium and host values: on the host (the
+// cached folds, then the *_host_one above) when scalar_on_host(), else on the device through the
+// scalar slot.  The outputs are the entry point's columns with ld = 1.
+// Air2IceRayTracing (in: txh, dist, depth, straight angle -- read when has_thr; status: optional).
+int solve_one(const airice_medium* m, int variant, double ice_h, const double in[4], bool has_thr,
+              double* out, uint8_t* status);
+// GetHorizontalDistanceToIntersectionPoint (in: src, dist, depth in cm).
+int hdtip_one(const airice_medium* m, double ice_cm, const double in[3], double out9[9],
+              uint8_t* ok);
+// TraceIceToAir (in: depth, ice, txh, dist).
+int trace_one(const airice_medium* m, const double in[4], double out10[10]);
+// The table lookup's minimizer fallback for a query that lk_query flagged one-sided
+// (.cc:1418-1420): out9 / *ok as the batch lookup.
 int lookup_fallback_one(const airice_medium* m, double src_cm, double dist_cm, double depth_cm,
                         double ice_cm, bool good, int flags, double out9[9], bool* ok);
 
@@ -167,7 +172,7 @@ enum LaunchId {
   LC_SCALAR_RAY,    // scalar_ray_kernel (one-query GetRayTracingSolutions)
   LC_ROOTS,         // roots_kernel / roots_sorted_kernel (batched root finder)
   LC_SCALAR_SOLVE,  // scalar_solve_kernel (one-query minimizer entry points)
-  LC_OUT,           // solve_out / hdtip_out / trace_out
+  LC_OUT,           // the batch stage-2 kernels: solve_out / hdtip_out / trace_out (launch_entry)
   LC_LOOKUP,        // lookup_kernel
   LC_RTF,           // rtf_kernel (ray layer, GSL-Brent search)
   LC_SINGLE_RAY,    // single_ray_kernel

@@ -9,16 +9,18 @@
 //  rays_kernel          : the same ray for arbitrary (angle, height) lists.
 //  scalar_ray_kernel    : one ray (n = 1) spread over a wave.
 // Minimizer (Air2IceRayTracing, .cc:1464-1616), two stages around one shared root finder
-// (RootSearch / solve_root, also compiled for the host's one-query calls):
+// (RootSearch / solve_root, also compiled for the host's one-query calls).  Its five entry points
+// -- Air2IceRayTracing in the MultiRay and the pythonwrapper variant, GetHorizontalDistanceTo-
+// IntersectionPoint, the table lookup's fallback, TraceIceToAir -- are each described once
+// (EntryPoint<OUT>: query source, park slots, stores); stage 2 (stage2_out), the kernels, the
+// launchers and the host route are written over that description.
 //  roots_kernel<IN>     : stage 1, one lane per query: bracket set-up, the 0.05-degree probe,
 //                         GSL-bisection replay (tolerance 1e-9, 40 iterations) over a THD-only
 //                         evaluator; each 1,024-query block sorted by straight-line angle in LDS.
 //  group_count_kernel<IN>, group_scatter_kernel<IN>, roots_sorted_kernel<IN> : stage 1 of large
 //                         trace batches, grouped across the whole batch first.
-//  solve_out_kernel<V>  : stage 2, one full evaluation at the parked root; VARIANT selects
-//                         MultiRay (dummy[17]) / pythonwrapper (dummy[15]) outputs.
-//  hdtip_out_kernel     : stage 2 of GetHorizontalDistanceToIntersectionPoint (.cc:945-989), cm.
-//  trace_out_kernel     : stage 2 of pythonwrapper TraceIceToAir (TraceIceToAir.C:5-73), rows of 10.
+//  solve_out_kernel<V>, hdtip_out_kernel, trace_out_kernel : stage 2 of a batch, one full
+//                         evaluation at the parked root, then the entry point's stores.
 //  scalar_solve_kernel<IN, OUT> : one query (n = 1), both stages in one launch on one wave.
 //  lookup_kernel        : the table lookup (.cc:1305-1462, airice_lookup.hpp); a lane that needs
 //                         the reference's minimizer fallback solves it in place.
@@ -1727,14 +1729,6 @@ constexpr int kRootsWaves = 4;  // 127 VGPRs: 4 waves/SIMD (5 and 6 spill and ru
 // the other sources stay block-local, AIRICE_GROUP_MIN in the environment overrides it)
 constexpr long long kGroupMin = 65536;
 
-// Stage 2 of the lookup fallback with the root handed over in registers (lookup_kernel):
-// defined below.
-__host__ __device__ __forceinline__ void fallback_out_direct(const DevMedium& M, const IceConsts& I,
-                                                    const QueryArgs& Q, double* __restrict__ out,
-                                                    size_t ld, uint8_t* __restrict__ ok,
-                                                    long long k, const double* tab,
-                                                    const Geometry& g, double root, int status);
-
 constexpr int kGroupAngles = 8;   // straight-line-angle classes (16 measured +0.4 %)
 // the classes within each angle class are the number of air layers the path spans (0-3+): a wave
 // then runs only the middle-layer segments its own queries have
@@ -1750,7 +1744,6 @@ struct GroupKey {
 template <int IN>
 __device__ __forceinline__ int query_bucket(const DevMedium& M, const QueryArgs& Q, long long k,
                                             const GroupKey& K) {
-  if (IN == IN_CM100 && !(Q.mask[k] & AIRICE_LOOKUP_FALLBACK)) return -1;  // not a fallback lane
   double thR_unused;
   const Geometry g = load_query<IN>(M, Q, k, thR_unused);
   const double den = g.H - g.ice - g.depth;
@@ -2002,65 +1995,226 @@ __device__ __forceinline__ void stage_log_table(double (*s)[2]) {
   __syncthreads();
 }
 
-// Stage 2 of Air2IceRayTracing: dummy[0..16] (MultiRay, .cc:1597-1614) or dummy[0..14]
-// (pythonwrapper, AirIceRayTracing.cc:1070-1084), SoA with stride ld.
-// Stage-2 bodies (one query k, parked root in its output slots), shared by the batch out kernels
-// and the one-query fused kernel (scalar_solve_kernel).
-// WAVE (one-query kernel): every lane runs the body with the root in wr; evaluate_root_wave
-// spreads the evaluation over the wave and lane 0 writes the outputs.
-// Stage-2 output stores (non-temporal stores measured no faster)
+// ---------------------------------------------------------------------------
+// Minimizer entry points.  EntryPoint<OUT> says everything that tells one from another:
+//  in            : its query source (IN_*);
+//  root, status  : where stage 1 parks query k's (root, status) in the output: the Park a launcher
+//                  passes (park_of) and the slots stage 2 reads back;
+//  write         : the stores of stage 2 for query k and its flag byte.
+// The stage-2 body, the kernels, the launchers and the host route below are written once over it.
+// ---------------------------------------------------------------------------
+enum { OUT_SOLVE_MR = 0, OUT_SOLVE_PY = 1, OUT_HDTIP = 2, OUT_FALLBACK = 3, OUT_TRACE = 4 };
+template <int OUT>
+struct EntryPoint;
+
+// Stage-2 output stores of the solve (non-temporal stores measured no faster)
 // (agent-scope stores: cfg3 solve call 0.2359-0.2370 -> 0.2352-0.2358 ms with the parked roots
 // stored the same way, same outputs; the lookup's non-temporal stores stay: 101.7 against 102.4 us)
 __host__ __device__ __forceinline__ void put_out(double* p, double v) { st_agent(p, v); }
 
-template <int VARIANT, bool WAVE = false>
-__host__ __device__ __forceinline__ void solve_out_body(const DevMedium& M, const IceConsts& I,
-                                               const QueryArgs& Q, double* __restrict__ out,
-                                               size_t ld, uint8_t* __restrict__ status,
-                                               long long k, const double* tab,
-                                               WaveRoot wr = WaveRoot{0.0, 0},
-                                               SortedPark sp = SortedPark{nullptr, nullptr}) {
+// Air2IceRayTracing: dummy[0..16] (MultiRay, .cc:1597-1614) or dummy[0..14] (pythonwrapper,
+// AirIceRayTracing.cc:1070-1084), SoA with stride ld; the flag byte takes the status bits.
+template <int VARIANT>
+struct SolveEntry {
+  static constexpr int in = IN_M;
+  __host__ __device__ static double* root(double* out, size_t ld, long long k) {
+    return out + 10 * ld + k;
+  }
+  __host__ __device__ static double* status(double* out, size_t, long long k) { return out + k; }
+  __host__ __device__ __forceinline__ static void write(const DevMedium& M, const IceConsts& I,
+                                                        const QueryArgs&, const Geometry& g,
+                                                        const Solved& S, double* __restrict__ out,
+                                                        size_t ld, uint8_t* __restrict__ status,
+                                                        long long k) {
+    const double thd = S.thd_ice + S.thd_air;
+    const double tt = S.t_ice + S.t_air;
+    put_out(out + 0 * ld + k, g.H);
+    put_out(out + 1 * ld + k, thd);
+    put_out(out + 2 * ld + k, S.thd_air);
+    put_out(out + 3 * ld + k, S.thd_ice);
+    put_out(out + 4 * ld + k, tt * kSpeedC);
+    put_out(out + 5 * ld + k, S.t_ice * kSpeedC);
+    put_out(out + 6 * ld + k, S.t_air * kSpeedC);
+    put_out(out + 7 * ld + k, tt);
+    put_out(out + 8 * ld + k, S.t_ice);
+    put_out(out + 9 * ld + k, S.t_air);
+    put_out(out + 10 * ld + k, S.launch);
+    if (VARIANT == AIRICE_VARIANT_MULTIRAY) {
+      double tS, tP;
+      fresnel_from_sine(S.ice_n, I.ice0.n, S.ice_n / I.ice0.n, sin_start(S.inc * M.d2r), tS, tP);
+      put_out(out + 11 * ld + k, S.ant);
+      put_out(out + 12 * ld + k, tS);
+      put_out(out + 13 * ld + k, tP);
+      put_out(out + 14 * ld + k, S.geo_air);
+      put_out(out + 15 * ld + k, S.geo_ice);
+      put_out(out + 16 * ld + k, S.inc);
+    } else {
+      put_out(out + 11 * ld + k, k_asin((S.ice_n / I.ice0.n) * sin_start(S.inc * M.d2r)) * M.r2d);
+      put_out(out + 12 * ld + k, S.ant);
+      put_out(out + 13 * ld + k, S.geo_air);
+      put_out(out + 14 * ld + k, S.geo_ice);
+    }
+    if (status != nullptr) status[k] = (uint8_t)S.status;
+  }
+};
+template <>
+struct EntryPoint<OUT_SOLVE_MR> : SolveEntry<AIRICE_VARIANT_MULTIRAY> {};
+template <>
+struct EntryPoint<OUT_SOLVE_PY> : SolveEntry<AIRICE_VARIANT_PYWRAPPER> {};
+
+// The park slots of the two entry points with 9 output columns (cm, rad) and a bool.
+struct Out9Slots {
+  __host__ __device__ static double* root(double* out9, size_t ld, long long k) {
+    return out9 + 4 * ld + k;
+  }
+  __host__ __device__ static double* status(double* out9, size_t, long long k) { return out9 + k; }
+};
+
+// GetHorizontalDistanceToIntersectionPoint (.cc:945-989).
+template <>
+struct EntryPoint<OUT_HDTIP> : Out9Slots {
+  static constexpr int in = IN_CM;
+  __host__ __device__ __forceinline__ static void write(const DevMedium& M, const IceConsts& I,
+                                                        const QueryArgs&, const Geometry& g,
+                                                        const Solved& S, double* __restrict__ out,
+                                                        size_t ld, uint8_t* __restrict__ ok,
+                                                        long long k) {
+    const double thd = S.thd_ice + S.thd_air;
+    double tS, tP;
+    fresnel_from_sine(S.ice_n, I.ice0.n, S.ice_n / I.ice0.n, sin_start(S.inc * M.d2r), tS, tP);
+    out[0 * ld + k] = (S.t_ice * kSpeedC) * 100;
+    out[1 * ld + k] = (S.t_air * kSpeedC) * 100;
+    out[2 * ld + k] = S.geo_ice * 100;
+    out[3 * ld + k] = S.geo_air * 100;
+    out[4 * ld + k] = S.launch * M.d2r;
+    out[5 * ld + k] = S.thd_air * 100;
+    out[6 * ld + k] = tS;
+    out[7 * ld + k] = tP;
+    out[8 * ld + k] = S.ant * M.d2r;
+    ok[k] = check_solution(thd, g.D) ? 1 : 0;
+  }
+};
+
+// The table lookup's minimizer fallback (.cc:1417-1456): the reference passes its own output
+// references to GetHorizontalDistanceToIntersectionPoint in the order (geoIce, geoAir, optIce,
+// optAir, ...), so the optical and geometric slots trade places; `ok` arrives holding the
+// lookup's checks and is completed with CheckSolBool and launchAngle < 0, then the four zeroed
+// slots of .cc:1451-1456.  Only queries flagged AIRICE_LOOKUP_FALLBACK (Q.mask) are solved, and
+// their root always reaches stage 2 in registers, so nothing is parked.
+template <>
+struct EntryPoint<OUT_FALLBACK> : Out9Slots {
+  static constexpr int in = IN_CM100;
+  __host__ __device__ __forceinline__ static void write(const DevMedium& M, const IceConsts& I,
+                                                        const QueryArgs&, const Geometry& g,
+                                                        const Solved& S, double* __restrict__ out,
+                                                        size_t ld, uint8_t* __restrict__ ok,
+                                                        long long k) {
+    const double thd = S.thd_ice + S.thd_air;
+    double tS, tP;
+    fresnel_from_sine(S.ice_n, I.ice0.n, S.ice_n / I.ice0.n, sin_start(S.inc * M.d2r), tS, tP);
+    const double launch = S.launch * M.d2r;
+    const bool good = ok[k] != 0 && check_solution(thd, g.D) && !(launch < 0);
+    out[0 * ld + k] = good ? S.geo_ice * 100 : 0.0;
+    out[1 * ld + k] = good ? S.geo_air * 100 : 0.0;
+    out[2 * ld + k] = (S.t_ice * kSpeedC) * 100;
+    out[3 * ld + k] = (S.t_air * kSpeedC) * 100;
+    out[4 * ld + k] = good ? launch : 0.0;
+    out[5 * ld + k] = good ? S.thd_air * 100 : 0.0;
+    out[6 * ld + k] = tS;
+    out[7 * ld + k] = tP;
+    out[8 * ld + k] = S.ant * M.d2r;
+    ok[k] = good ? 1 : 0;
+  }
+};
+
+// The pythonwrapper TraceIceToAir (TraceIceToAir.C:5-73): rows of 10, no flag byte, no ld.
+template <>
+struct EntryPoint<OUT_TRACE> {
+  static constexpr int in = IN_TRACE;
+  __host__ __device__ static double* root(double* out10, size_t, long long k) {
+    return out10 + 10 * k + 5;
+  }
+  __host__ __device__ static double* status(double* out10, size_t, long long k) {
+    return out10 + 10 * k + 9;
+  }
+  __host__ __device__ __forceinline__ static void write(const DevMedium& M, const IceConsts& I,
+                                                        const QueryArgs&, const Geometry& g,
+                                                        const Solved& S, double* __restrict__ out10,
+                                                        size_t, uint8_t*, long long k) {
+    double* o = out10 + 10 * k;
+    const double thd = S.thd_ice + S.thd_air;
+    const double aoi = k_asin((S.ice_n / I.ice0.n) * sin_start(S.inc * M.d2r)) * M.r2d;
+    if (check_solution(thd, g.D)) {
+      // swap(launch, received); received = 180 - received (TraceIceToAir.C:33-34)
+      o[0] = g.H;
+      o[1] = g.D;
+      o[2] = S.geo_ice;
+      o[3] = S.geo_air;
+      o[4] = S.ant;
+      o[5] = 180 - S.launch;
+      o[6] = S.thd_air;
+      o[7] = aoi;
+      o[8] = 0;
+      o[9] = 0;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 10; ++c) o[c] = -1000;
+    }
+  }
+};
+
+// Where stage 1 of entry point OUT parks, as its launcher passes it to the stage-1 kernels.
+template <int OUT>
+static Park park_of(double* out, size_t ld) {
+  using E = EntryPoint<OUT>;
+  // (the stride: from query 0's slot to query 1's)
+  return Park{E::root(out, ld, 0), E::status(out, ld, 0), E::root(out, ld, 1) - E::root(out, ld, 0),
+              bisect_exact(), nullptr};
+}
+
+// Stage 2 of every entry point for one query k: one full evaluation at the root, then the entry
+// point's stores.  Where the query and its root come from:
+//  AT_PARKED : the lane reloads the query and reads the root stage 1 parked (the batch kernels);
+//  AT_WAVE   : wr holds them on every lane of the one-query kernel; evaluate_root_wave spreads the
+//              evaluation over the wave and lane 0 writes;
+//  AT_DIRECT : wr holds them, one lane (lookup_kernel's fallback lanes, the host route).
+enum { AT_PARKED = 0, AT_WAVE = 1, AT_DIRECT = 2 };
+template <int OUT, int MODE>
+__host__ __device__ __forceinline__ void stage2_out(const DevMedium& M, const IceConsts& I,
+                                                    const QueryArgs& Q, double* __restrict__ out,
+                                                    size_t ld, uint8_t* __restrict__ flag,
+                                                    long long k, const double* tab,
+                                                    WaveRoot wr = WaveRoot{0.0, 0},
+                                                    SortedPark sp = SortedPark{nullptr, nullptr}) {
+  using E = EntryPoint<OUT>;
+  // (the fallback's callers have looked at the query's flag already: only flagged ones get here)
+  static_assert(solves_every_lane(E::in) || MODE != AT_PARKED, "the fallback parks nothing");
   double thR;
-  const Geometry g = WAVE ? wr.g : load_query<IN_M>(M, Q, k, thR);
+  const Geometry g = MODE != AT_PARKED ? wr.g : load_query<E::in>(M, Q, k, thR);
   double x = wr.root;
   int st = wr.status;
-  if (!WAVE) parked(sp, out + 10 * ld + k, out + 0 * ld + k, k, x, st);
+  if (MODE == AT_PARKED)
+    parked(sp, E::root(out, ld, k), E::status(out, ld, k), k, x, st);
   Solved S;
-  if constexpr (WAVE) {
+  if constexpr (MODE == AT_WAVE) {
     S = evaluate_root_wave(M, I, g, x, st, tab);
     if (threadIdx.x != 0) return;
   } else {
     S = evaluate_root(M, I, g, x, st, tab);
   }
-  const double thd = S.thd_ice + S.thd_air;
-  const double tt = S.t_ice + S.t_air;
-  put_out(out + 0 * ld + k, g.H);
-  put_out(out + 1 * ld + k, thd);
-  put_out(out + 2 * ld + k, S.thd_air);
-  put_out(out + 3 * ld + k, S.thd_ice);
-  put_out(out + 4 * ld + k, tt * kSpeedC);
-  put_out(out + 5 * ld + k, S.t_ice * kSpeedC);
-  put_out(out + 6 * ld + k, S.t_air * kSpeedC);
-  put_out(out + 7 * ld + k, tt);
-  put_out(out + 8 * ld + k, S.t_ice);
-  put_out(out + 9 * ld + k, S.t_air);
-  put_out(out + 10 * ld + k, S.launch);
-  if (VARIANT == AIRICE_VARIANT_MULTIRAY) {
-    double tS, tP;
-    fresnel_from_sine(S.ice_n, I.ice0.n, S.ice_n / I.ice0.n, sin_start(S.inc * M.d2r), tS, tP);
-    put_out(out + 11 * ld + k, S.ant);
-    put_out(out + 12 * ld + k, tS);
-    put_out(out + 13 * ld + k, tP);
-    put_out(out + 14 * ld + k, S.geo_air);
-    put_out(out + 15 * ld + k, S.geo_ice);
-    put_out(out + 16 * ld + k, S.inc);
-  } else {
-    put_out(out + 11 * ld + k, k_asin((S.ice_n / I.ice0.n) * sin_start(S.inc * M.d2r)) * M.r2d);
-    put_out(out + 12 * ld + k, S.ant);
-    put_out(out + 13 * ld + k, S.geo_air);
-    put_out(out + 14 * ld + k, S.geo_ice);
-  }
-  if (status != nullptr) status[k] = (uint8_t)S.status;
+  E::write(M, I, Q, g, S, out, ld, flag, k);
+}
+
+// The batch stage-2 kernels: one query per lane, the log table read from LDS like the solve.
+template <int OUT>
+__device__ __forceinline__ void out_block(const DevMedium& M, const IceConsts& I,
+                                          const QueryArgs& Q, double* __restrict__ out, size_t ld,
+                                          uint8_t* __restrict__ flag, const SortedPark& sp) {
+  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
+  __shared__ __align__(16) double s_logtab[1 << kLogTableBits][2];
+  stage_log_table(s_logtab);
+  if (k >= Q.n) return;
+  stage2_out<OUT, AT_PARKED>(M, I, Q, out, ld, flag, k, &s_logtab[0][0], WaveRoot{0.0, 0}, sp);
 }
 
 // occupancy of the stage-2 kernel: the compiler's choice (104 VGPRs, 4 waves/SIMD; held to 5-6
@@ -2070,167 +2224,32 @@ __global__ __launch_bounds__(kBlock, kOutWaves) void solve_out_kernel(DevMedium 
                                                            double* __restrict__ out, size_t ld,
                                                            uint8_t* __restrict__ status,
                                                            SortedPark sp) {
-  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
-  __shared__ __align__(16) double s_logtab[1 << kLogTableBits][2];
-  stage_log_table(s_logtab);
-  if (k >= Q.n) return;
-  solve_out_body<VARIANT>(M, I, Q, out, ld, status, k, &s_logtab[0][0], WaveRoot{0.0, 0}, sp);
-}
-
-// Stage 2 of GetHorizontalDistanceToIntersectionPoint (.cc:945-989): 9 outputs (cm, rad) + bool.
-template <bool WAVE = false>
-__host__ __device__ __forceinline__ void hdtip_out_body(const DevMedium& M, const IceConsts& I,
-                                               const QueryArgs& Q, double* __restrict__ out,
-                                               size_t ld, uint8_t* __restrict__ ok, long long k,
-                                               const double* tab, WaveRoot wr = WaveRoot{0.0, 0},
-                                               SortedPark sp = SortedPark{nullptr, nullptr}) {
-  double thR;
-  const Geometry g = WAVE ? wr.g : load_query<IN_CM>(M, Q, k, thR);
-  double x = wr.root;
-  int st = wr.status;
-  if (!WAVE) parked(sp, out + 4 * ld + k, out + 0 * ld + k, k, x, st);
-  Solved S;
-  if constexpr (WAVE) {
-    S = evaluate_root_wave(M, I, g, x, st, tab);
-    if (threadIdx.x != 0) return;
-  } else {
-    S = evaluate_root(M, I, g, x, st, tab);
-  }
-  const double thd = S.thd_ice + S.thd_air;
-  double tS, tP;
-  fresnel_from_sine(S.ice_n, I.ice0.n, S.ice_n / I.ice0.n, sin_start(S.inc * M.d2r), tS, tP);
-  out[0 * ld + k] = (S.t_ice * kSpeedC) * 100;
-  out[1 * ld + k] = (S.t_air * kSpeedC) * 100;
-  out[2 * ld + k] = S.geo_ice * 100;
-  out[3 * ld + k] = S.geo_air * 100;
-  out[4 * ld + k] = S.launch * M.d2r;
-  out[5 * ld + k] = S.thd_air * 100;
-  out[6 * ld + k] = tS;
-  out[7 * ld + k] = tP;
-  out[8 * ld + k] = S.ant * M.d2r;
-  ok[k] = check_solution(thd, g.D) ? 1 : 0;
+  out_block<VARIANT == AIRICE_VARIANT_MULTIRAY ? OUT_SOLVE_MR : OUT_SOLVE_PY>(M, I, Q, out, ld,
+                                                                              status, sp);
 }
 
 __global__ __launch_bounds__(kBlock, kOutWaves) void hdtip_out_kernel(DevMedium M, IceConsts I, QueryArgs Q,
                                                            double* __restrict__ out, size_t ld,
                                                            uint8_t* __restrict__ ok, SortedPark sp) {
-  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
-  __shared__ __align__(16) double s_logtab[1 << kLogTableBits][2];
-  stage_log_table(s_logtab);
-  if (k >= Q.n) return;
-  hdtip_out_body(M, I, Q, out, ld, ok, k, &s_logtab[0][0], WaveRoot{0.0, 0}, sp);
-}
-
-// Stage 2 of the table lookup's minimizer fallback (.cc:1417-1456): the reference passes its
-// own output references to GetHorizontalDistanceToIntersectionPoint in the order
-// (geoIce, geoAir, optIce, optAir, ...), so the optical and geometric slots trade places;
-// `ok` arrives holding the lookup's checks and is completed with CheckSolBool and
-// launchAngle < 0, then the four zeroed slots of .cc:1451-1456.
-// DIRECT (lane form): the query and its root arrive in wr (the fused fallback pass) instead of
-// being reloaded and read back from the parked slots.
-template <bool WAVE = false, bool DIRECT = false>
-__host__ __device__ __forceinline__ void lookup_fallback_out_body(const DevMedium& M, const IceConsts& I,
-                                                         const QueryArgs& Q,
-                                                         double* __restrict__ out, size_t ld,
-                                                         uint8_t* __restrict__ ok, long long k,
-                                                         const double* tab,
-                                                         WaveRoot wr = WaveRoot{0.0, 0}) {
-  if (!(Q.mask[k] & AIRICE_LOOKUP_FALLBACK)) return;
-  double thR;
-  const Geometry g = (WAVE || DIRECT) ? wr.g : load_query<IN_CM100>(M, Q, k, thR);
-  const double x = (WAVE || DIRECT) ? wr.root : out[4 * ld + k];
-  const int st = (WAVE || DIRECT) ? wr.status : (int)out[0 * ld + k];
-  Solved S;
-  if constexpr (WAVE) {
-    S = evaluate_root_wave(M, I, g, x, st, tab);
-    if (threadIdx.x != 0) return;
-  } else {
-    S = evaluate_root(M, I, g, x, st, tab);
-  }
-  const double thd = S.thd_ice + S.thd_air;
-  double tS, tP;
-  fresnel_from_sine(S.ice_n, I.ice0.n, S.ice_n / I.ice0.n, sin_start(S.inc * M.d2r), tS, tP);
-  const double launch = S.launch * M.d2r;
-  const bool good = ok[k] != 0 && check_solution(thd, g.D) && !(launch < 0);
-  out[0 * ld + k] = good ? S.geo_ice * 100 : 0.0;
-  out[1 * ld + k] = good ? S.geo_air * 100 : 0.0;
-  out[2 * ld + k] = (S.t_ice * kSpeedC) * 100;
-  out[3 * ld + k] = (S.t_air * kSpeedC) * 100;
-  out[4 * ld + k] = good ? launch : 0.0;
-  out[5 * ld + k] = good ? S.thd_air * 100 : 0.0;
-  out[6 * ld + k] = tS;
-  out[7 * ld + k] = tP;
-  out[8 * ld + k] = S.ant * M.d2r;
-  ok[k] = good ? 1 : 0;
-}
-
-__host__ __device__ __forceinline__ void fallback_out_direct(const DevMedium& M, const IceConsts& I,
-                                                    const QueryArgs& Q, double* __restrict__ out,
-                                                    size_t ld, uint8_t* __restrict__ ok,
-                                                    long long k, const double* tab,
-                                                    const Geometry& g, double root, int status) {
-  lookup_fallback_out_body<false, true>(M, I, Q, out, ld, ok, k, tab, WaveRoot{root, status, g});
-}
-
-// Stage 2 of the pythonwrapper TraceIceToAir (TraceIceToAir.C:5-73), rows of 10.
-template <bool WAVE = false>
-__host__ __device__ __forceinline__ void trace_out_body(const DevMedium& M, const IceConsts& I,
-                                               const QueryArgs& Q, double* __restrict__ out10,
-                                               long long k, const double* tab,
-                                               WaveRoot wr = WaveRoot{0.0, 0},
-                                               SortedPark sp = SortedPark{nullptr, nullptr}) {
-  double thR;
-  const Geometry g = WAVE ? wr.g : load_query<IN_TRACE>(M, Q, k, thR);
-  double* o = out10 + 10 * k;
-  double x = wr.root;
-  int st = wr.status;
-  if (!WAVE) parked(sp, o + 5, o + 9, k, x, st);
-  Solved S;
-  if constexpr (WAVE) {
-    S = evaluate_root_wave(M, I, g, x, st, tab);
-    if (threadIdx.x != 0) return;
-  } else {
-    S = evaluate_root(M, I, g, x, st, tab);
-  }
-  const double thd = S.thd_ice + S.thd_air;
-  const double aoi = k_asin((S.ice_n / I.ice0.n) * sin_start(S.inc * M.d2r)) * M.r2d;
-  if (check_solution(thd, g.D)) {
-    // swap(launch, received); received = 180 - received (TraceIceToAir.C:33-34)
-    o[0] = g.H;
-    o[1] = g.D;
-    o[2] = S.geo_ice;
-    o[3] = S.geo_air;
-    o[4] = S.ant;
-    o[5] = 180 - S.launch;
-    o[6] = S.thd_air;
-    o[7] = aoi;
-    o[8] = 0;
-    o[9] = 0;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 10; ++c) o[c] = -1000;
-  }
+  out_block<OUT_HDTIP>(M, I, Q, out, ld, ok, sp);
 }
 
 __global__ __launch_bounds__(kBlock, kTraceOutWaves) void trace_out_kernel(DevMedium M, IceConsts I, QueryArgs Q,
                                                            double* __restrict__ out10,
                                                            SortedPark sp) {
-  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
-  __shared__ __align__(16) double s_logtab[1 << kLogTableBits][2];
-  stage_log_table(s_logtab);
-  if (k >= Q.n) return;
-  trace_out_body(M, I, Q, out10, k, &s_logtab[0][0], WaveRoot{0.0, 0}, sp);
+  out_block<OUT_TRACE>(M, I, Q, out10, 0, nullptr, sp);
 }
 
 // One query, both stages in one launch (the scalar C++ / ctypes entry points): one wave finds the
-// root with the evaluation spread over its lanes, then runs the stage-2 body of the entry point
-// (OUT) with its evaluation spread the same way.  Bit-identical to the two batch kernels.
-enum { OUT_SOLVE_MR = 0, OUT_SOLVE_PY = 1, OUT_HDTIP = 2, OUT_FALLBACK = 3, OUT_TRACE = 4 };
+// root with the evaluation spread over its lanes, then runs stage 2 of the entry point (OUT) with
+// its evaluation spread the same way.  Bit-identical to the two batch kernels.
+// (IN is EntryPoint<OUT>::in; of park only the exact flag is used: the root goes to stage 2
+// directly)
 template <int IN, int OUT>
-// (of park only the exact flag is used: the root goes to the stage-2 body directly)
 __global__ __launch_bounds__(64) void scalar_solve_kernel(DevMedium M, IceConsts I, QueryArgs Q,
                                                           Park park, double* out, size_t ld,
                                                           uint8_t* flag, Signal sig) {
+  static_assert(IN == EntryPoint<OUT>::in, "the entry point fixes its query source");
   prefetch_kernargs<sizeof(DevMedium) + sizeof(IceConsts)>();
   // one wave and a handful of logarithms per evaluation: the log table is read from global
   // memory (L1 / L2 after the first call) instead of being staged in LDS first
@@ -2240,81 +2259,57 @@ __global__ __launch_bounds__(64) void scalar_solve_kernel(DevMedium M, IceConsts
     return;
   }
   double thR;
-  const Geometry g = load_query<IN>(M, Q, 0, thR, 
+  const Geometry g = load_query<IN>(M, Q, 0, thR,
                                     sig.n_in >= ((IN == IN_TRACE || (IN == IN_M && Q.d != nullptr)) ? 4 : 3)
                                         ? &sig
                                         : nullptr);
   const SolveResult r = solve_root<true>(M, I, g, thR, park.exact != 0, tab);
-  // every lane runs the stage-2 body (its evaluation spread over the wave); lane 0 writes
-  const WaveRoot wr{r.root, r.status, g};
-  if (OUT == OUT_SOLVE_MR)
-    solve_out_body<AIRICE_VARIANT_MULTIRAY, true>(M, I, Q, out, ld, flag, 0, tab, wr);
-  if (OUT == OUT_SOLVE_PY)
-    solve_out_body<AIRICE_VARIANT_PYWRAPPER, true>(M, I, Q, out, ld, flag, 0, tab, wr);
-  if (OUT == OUT_HDTIP) hdtip_out_body<true>(M, I, Q, out, ld, flag, 0, tab, wr);
-  if (OUT == OUT_FALLBACK) lookup_fallback_out_body<true>(M, I, Q, out, ld, flag, 0, tab, wr);
-  if (OUT == OUT_TRACE) trace_out_body<true>(M, I, Q, out, 0, tab, wr);
+  // every lane runs stage 2 (its evaluation spread over the wave); lane 0 writes
+  stage2_out<OUT, AT_WAVE>(M, I, Q, out, ld, flag, 0, tab, WaveRoot{r.root, r.status, g});
   if (threadIdx.x != 0) return;
   signal_done(sig);
 }
 
 // One query of a minimizer entry point on the host (AIRICE_SCALAR_HOST, the default of the
-// one-query C++ / ctypes drop-ins): the root finder and the entry point's stage-2 body compiled
-// for the CPU from the same source as the batch kernels (the host's correctly rounded sqrt and
-// quotients in place of the device iterations).  The root is the GSL bisection's, decided by the
-// signs of f at its midpoints, so it is the device's; the outputs at it agree to an ulp or so.
-// Q: the query at index 0 (host pointers); park: where stage 1 parks (root, status) for the body,
-// as the launcher of the batch path sets it.
-template <int IN, int OUT>
-static void solve_one_host_t(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
-                             const Park& park, double* out, size_t ld, uint8_t* flag) {
+// one-query C++ / ctypes drop-ins): the root finder and stage 2 compiled for the CPU from the same
+// source as the batch kernels (the host's correctly rounded sqrt and quotients in place of the
+// device iterations).  The root is the GSL bisection's, decided by the signs of f at its
+// midpoints, so it is the device's; the outputs at it agree to an ulp or so.
+// Q: the query at index 0 (host pointers); out, ld, flag: as the entry point's launcher takes them.
+template <int OUT>
+static int solve_one_host_t(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
+                            double* out, size_t ld, uint8_t* flag) {
+  constexpr int IN = EntryPoint<OUT>::in;
   const double* tab = &kLogTable[0][0];
-  if (IN == IN_CM100 && !(Q.mask[0] & AIRICE_LOOKUP_FALLBACK)) return;
+  if (IN == IN_CM100 && !(Q.mask[0] & AIRICE_LOOKUP_FALLBACK)) return AIRICE_OK;
   double thR;
   const Geometry g = load_query<IN>(M, Q, 0, thR);
-  const SolveResult r = solve_root<false>(M, I, g, thR, park.exact != 0, tab);
-  if constexpr (OUT == OUT_FALLBACK) {
-    fallback_out_direct(M, I, Q, out, ld, flag, 0, tab, g, r.root, r.status);
-  } else {
-    park.root[0] = r.root;
-    park.status[0] = (double)r.status;
-    if constexpr (OUT == OUT_SOLVE_MR)
-      solve_out_body<AIRICE_VARIANT_MULTIRAY>(M, I, Q, out, ld, flag, 0, tab);
-    if constexpr (OUT == OUT_SOLVE_PY)
-      solve_out_body<AIRICE_VARIANT_PYWRAPPER>(M, I, Q, out, ld, flag, 0, tab);
-    if constexpr (OUT == OUT_HDTIP) hdtip_out_body(M, I, Q, out, ld, flag, 0, tab);
-    if constexpr (OUT == OUT_TRACE) trace_out_body(M, I, Q, out, 0, tab);
-  }
+  const SolveResult r = solve_root<false>(M, I, g, thR, bisect_exact() != 0, tab);
+  stage2_out<OUT, AT_DIRECT>(M, I, Q, out, ld, flag, 0, tab, WaveRoot{r.root, r.status, g});
+  return AIRICE_OK;
 }
 
 // Air2IceRayTracing, one query (in: txh, dist, depth [, straight angle]): out17 / out15 with
-// ld = 1 (as launch_solve parks and writes), status bits.
+// ld = 1, status bits.
 int solve_host_one(const DevMedium& M, const IceConsts& I, int variant, const double* in,
                    bool has_thr, double* out, uint8_t* status) {
   const QueryArgs Q{in, in + 1, in + 2, has_thr ? in + 3 : nullptr, I.ice_h, 1};
-  const Park park{out + 10, out, 1, bisect_exact(), nullptr};
-  if (variant == AIRICE_VARIANT_PYWRAPPER)
-    solve_one_host_t<IN_M, OUT_SOLVE_PY>(M, I, Q, park, out, 1, status);
-  else
-    solve_one_host_t<IN_M, OUT_SOLVE_MR>(M, I, Q, park, out, 1, status);
-  return AIRICE_OK;
+  return variant == AIRICE_VARIANT_PYWRAPPER
+             ? solve_one_host_t<OUT_SOLVE_PY>(M, I, Q, out, 1, status)
+             : solve_one_host_t<OUT_SOLVE_MR>(M, I, Q, out, 1, status);
 }
 
 // GetHorizontalDistanceToIntersectionPoint, one query (in: src, dist, depth in cm).
 int hdtip_host_one(const DevMedium& M, const IceConsts& I, double ice_cm, const double* in,
                    double* out9, uint8_t* ok) {
-  const QueryArgs Q{in, in + 1, in + 2, nullptr, ice_cm, 1};
-  const Park park{out9 + 4, out9, 1, bisect_exact(), nullptr};
-  solve_one_host_t<IN_CM, OUT_HDTIP>(M, I, Q, park, out9, 1, ok);
-  return AIRICE_OK;
+  return solve_one_host_t<OUT_HDTIP>(M, I, QueryArgs{in, in + 1, in + 2, nullptr, ice_cm, 1}, out9,
+                                     1, ok);
 }
 
 // TraceIceToAir, one query (in: depth, ice, txh, dist).
 int trace_host_one(const DevMedium& M, const IceConsts& I, const double* in, double* out10) {
-  const QueryArgs Q{in, in + 1, in + 2, in + 3, 0.0, 1};
-  const Park park{out10 + 5, out10 + 9, 10, bisect_exact(), nullptr};
-  solve_one_host_t<IN_TRACE, OUT_TRACE>(M, I, Q, park, out10, 0, nullptr);
-  return AIRICE_OK;
+  return solve_one_host_t<OUT_TRACE>(M, I, QueryArgs{in, in + 1, in + 2, in + 3, 0.0, 1}, out10, 0,
+                                     nullptr);
 }
 
 // QueryArgs::ice of the IN_CM100 source: .cc:1309 turns IceLayerHeight into metres and .cc:1419
@@ -2326,9 +2321,7 @@ static inline double fallback_ice_arg(double ice_cm) { return (ice_cm / 100) * 1
 int lookup_fallback_host_one(const DevMedium& M, const IceConsts& I, double ice_cm,
                              const double* in, double* out9, uint8_t* ok, const uint8_t* flags) {
   const QueryArgs Q{in, in + 1, in + 2, nullptr, fallback_ice_arg(ice_cm), 1, flags};
-  const Park park{out9 + 4, out9, 1, bisect_exact(), nullptr};
-  solve_one_host_t<IN_CM100, OUT_FALLBACK>(M, I, Q, park, out9, 1, ok);
-  return AIRICE_OK;
+  return solve_one_host_t<OUT_FALLBACK>(M, I, Q, out9, 1, ok);
 }
 
 // ---------------------------------------------------------------------------
@@ -2462,29 +2455,43 @@ struct RootsScratch {
   }
 };
 
-// The two stages of a minimizer batch on one stream: launch_roots<IN>, then between() (launch_solve's
-// statistics dump; non-zero ends the launch), then the stage-2 kernel, which out(sp) enqueues, and
-// the release of a grouped launch's scratch behind it.
-template <int IN, class Out, class Between>
-static int launch_stages(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
-                         const Park& park, hipStream_t st, Out out, Between between) {
+// One query of entry point OUT on the device: scalar_solve_kernel, which takes the armed signal
+// of a one-query call (take_scalar_signal).
+template <int OUT>
+static int launch_one_wave(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
+                           const Park& park, double* out, size_t ld, uint8_t* flag,
+                           hipStream_t st) {
+  count_launch(LC_SCALAR_SOLVE);
+  hipLaunchKernelGGL((scalar_solve_kernel<EntryPoint<OUT>::in, OUT>), dim3(1), dim3(64), 0, st, M,
+                     I, Q, park, out, ld, flag, take_scalar_signal());
+  return launch_ok();
+}
+
+// A minimizer launch of entry point OUT on one stream.  One query takes the one-wave kernel
+// (never a statistics run: its counts come from roots_kernel).  A batch takes the two stages:
+// launch_roots, then between() (launch_solve's statistics dump; non-zero ends the launch), then
+// the stage-2 kernel, which stage2(grid, block, sp) enqueues, and the release of a grouped
+// launch's scratch behind it.
+template <int OUT, class Stage2, class Between>
+static int launch_entry(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
+                        const Park& park, double* out, size_t ld, uint8_t* flag, hipStream_t st,
+                        Stage2 stage2, Between between) {
+  if (Q.n == 1 && park.stats == nullptr)
+    return launch_one_wave<OUT>(M, I, Q, park, out, ld, flag, st);
   SortedPark sp;
   RootsScratch scr(st);
-  if (int rc = launch_roots<IN>(M, I, Q, park, (size_t)Q.n, st, sp, scr.ws)) return rc;
+  if (int rc = launch_roots<EntryPoint<OUT>::in>(M, I, Q, park, (size_t)Q.n, st, sp, scr.ws))
+    return rc;
   if (int rc = between()) return rc;
   ktimer_begin(KT_OUT, st);
   count_launch(LC_OUT);
-  out(sp);
+  stage2(dim3(grid_for(Q.n)), dim3(kBlock), sp);
   ktimer_end(KT_OUT, st);
   const int rc = launch_ok();
   if (int rf = scr.release()) return rf;
   return rc;
 }
-template <int IN, class Out>
-static int launch_stages(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
-                         const Park& park, hipStream_t st, Out out) {
-  return launch_stages<IN>(M, I, Q, park, st, out, [] { return AIRICE_OK; });
-}
+static int no_hook() { return AIRICE_OK; }  // between(), for the launchers without one
 
 // Per-grid device caches of the table launch: the row constants of every Tx-height row
 // (RowConst, 104 B; rowconst_kernel) and the start-angle sine of every grid column (8 B;
@@ -2930,22 +2937,10 @@ int launch_solve(const DevMedium& M, const IceConsts& I, int variant, const doub
                  double* out, size_t ld, uint8_t* status, hipStream_t st) {
   if (n == 0) return AIRICE_OK;
   const QueryArgs Q{txh, dist, depth, thr, I.ice_h, (long long)n};
-  Park park{out + 10 * ld, out, 1, bisect_exact(), nullptr};
+  Park park = park_of<OUT_SOLVE_MR>(out, ld);  // (both variants park alike)
   static const char* stats_path = getenv("AIRICE_SOLVE_STATS");
   if (stats_path != nullptr && hipMalloc(&park.stats, sizeof(int) * kStatsInts * n) != hipSuccess)
     return AIRICE_EHIP;
-  const dim3 grid(grid_for((long long)n)), block(kBlock);
-  if (n == 1 && park.stats == nullptr) {
-    const Signal sig = take_scalar_signal();
-    count_launch(LC_SCALAR_SOLVE);
-    if (variant == AIRICE_VARIANT_MULTIRAY)
-      hipLaunchKernelGGL((scalar_solve_kernel<IN_M, OUT_SOLVE_MR>), dim3(1), dim3(64), 0, st, M, I,
-                         Q, park, out, ld, status, sig);
-    else
-      hipLaunchKernelGGL((scalar_solve_kernel<IN_M, OUT_SOLVE_PY>), dim3(1), dim3(64), 0, st, M, I,
-                         Q, park, out, ld, status, sig);
-    return launch_ok();
-  }
   auto dump_stats = [&] {  // debug: append the per-query counts (synchronous)
     if (park.stats == nullptr) return AIRICE_OK;
     std::vector<int> h(kStatsInts * n);
@@ -2959,14 +2954,14 @@ int launch_solve(const DevMedium& M, const IceConsts& I, int variant, const doub
     }
     return AIRICE_OK;
   };
-  auto stage2 = variant == AIRICE_VARIANT_MULTIRAY ? solve_out_kernel<AIRICE_VARIANT_MULTIRAY>
-                                                   : solve_out_kernel<AIRICE_VARIANT_PYWRAPPER>;
-  return launch_stages<IN_M>(
-      M, I, Q, park, st,
-      [&](const SortedPark& sp) {
-        hipLaunchKernelGGL(stage2, grid, block, 0, st, M, I, Q, out, ld, status, sp);
-      },
-      dump_stats);
+  const bool mr = variant == AIRICE_VARIANT_MULTIRAY;
+  auto kernel = mr ? solve_out_kernel<AIRICE_VARIANT_MULTIRAY>
+                   : solve_out_kernel<AIRICE_VARIANT_PYWRAPPER>;
+  auto stage2 = [&](dim3 grid, dim3 block, const SortedPark& sp) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, M, I, Q, out, ld, status, sp);
+  };
+  return mr ? launch_entry<OUT_SOLVE_MR>(M, I, Q, park, out, ld, status, st, stage2, dump_stats)
+            : launch_entry<OUT_SOLVE_PY>(M, I, Q, park, out, ld, status, st, stage2, dump_stats);
 }
 
 int launch_hdtip(const DevMedium& M, const IceConsts& I, const double* src, const double* dist,
@@ -2974,36 +2969,21 @@ int launch_hdtip(const DevMedium& M, const IceConsts& I, const double* src, cons
                  uint8_t* ok, hipStream_t st) {
   if (n == 0) return AIRICE_OK;
   const QueryArgs Q{src, dist, depth, nullptr, ice_cm, (long long)n};
-  const Park park{out + 4 * ld, out, 1, bisect_exact(), nullptr};
-  const dim3 grid(grid_for((long long)n)), block(kBlock);
-  if (n == 1) {
-    count_launch(LC_SCALAR_SOLVE);
-    hipLaunchKernelGGL((scalar_solve_kernel<IN_CM, OUT_HDTIP>), dim3(1), dim3(64), 0, st, M, I, Q,
-                       park, out, ld, ok, take_scalar_signal());
-    return launch_ok();
-  }
-  return launch_stages<IN_CM>(M, I, Q, park, st, [&](const SortedPark& sp) {
-    hipLaunchKernelGGL(hdtip_out_kernel, grid, block, 0, st, M, I, Q, out, ld, ok, sp);
-  });
+  return launch_entry<OUT_HDTIP>(
+      M, I, Q, park_of<OUT_HDTIP>(out, ld), out, ld, ok, st,
+      [&](dim3 grid, dim3 block, const SortedPark& sp) {
+        hipLaunchKernelGGL(hdtip_out_kernel, grid, block, 0, st, M, I, Q, out, ld, ok, sp);
+      },
+      no_hook);
 }
 
 // The table lookup's minimizer fallback for one query (the one-query device call; a batch solves
 // its fallback lanes inside lookup_kernel).
 int launch_lookup_fallback(const DevMedium& M, const IceConsts& I, const double* src,
-                           const double* dist, const double* depth, double ice_cm, size_t n,
-                           double* out, size_t ld, uint8_t* ok, const uint8_t* flags,
-                           hipStream_t st) {
-  if (n == 0) return AIRICE_OK;
-  const QueryArgs Q{src, dist, depth, nullptr, fallback_ice_arg(ice_cm), (long long)n, flags};
-  const Park park{out + 4 * ld, out, 1, bisect_exact(), nullptr};
-  if (n != 1) {
-    set_error("launch_lookup_fallback: one query (batches solve their fallback in lookup_kernel)");
-    return AIRICE_EINVAL;
-  }
-  count_launch(LC_SCALAR_SOLVE);
-  hipLaunchKernelGGL((scalar_solve_kernel<IN_CM100, OUT_FALLBACK>), dim3(1), dim3(64), 0, st, M,
-                     I, Q, park, out, ld, ok, take_scalar_signal());
-  return launch_ok();
+                           const double* dist, const double* depth, double ice_cm, double* out,
+                           size_t ld, uint8_t* ok, const uint8_t* flags, hipStream_t st) {
+  const QueryArgs Q{src, dist, depth, nullptr, fallback_ice_arg(ice_cm), 1, flags};
+  return launch_one_wave<OUT_FALLBACK>(M, I, Q, park_of<OUT_FALLBACK>(out, ld), out, ld, ok, st);
 }
 
 // GetHorizontalDistanceToIntersectionPoint_Table (.cc:1305-1462) for a batch, one query per lane:
@@ -3037,7 +3017,8 @@ __global__ __launch_bounds__(kLkBlock, kRootsWaves) void lookup_kernel(
     double thR;
     const Geometry g = load_query<IN_CM100>(M, Q, k, thR);
     const SolveResult r = solve_root(M, I, g, thR, exact != 0, &kLogTable[0][0]);
-    fallback_out_direct(M, I, Q, out, ld, ok, k, &kLogTable[0][0], g, r.root, r.status);
+    stage2_out<OUT_FALLBACK, AT_DIRECT>(M, I, Q, out, ld, ok, k, &kLogTable[0][0],
+                                        WaveRoot{r.root, r.status, g});
   }
 }
 
@@ -3060,17 +3041,12 @@ int launch_trace(const DevMedium& M, const IceConsts& I, const double* depth, co
                  const double* txh, const double* dist, size_t n, double* out10, hipStream_t st) {
   if (n == 0) return AIRICE_OK;
   const QueryArgs Q{depth, ice, txh, dist, 0.0, (long long)n};
-  const Park park{out10 + 5, out10 + 9, 10, bisect_exact(), nullptr};
-  const dim3 grid(grid_for((long long)n)), block(kBlock);
-  if (n == 1) {
-    count_launch(LC_SCALAR_SOLVE);
-    hipLaunchKernelGGL((scalar_solve_kernel<IN_TRACE, OUT_TRACE>), dim3(1), dim3(64), 0, st, M, I, Q,
-                       park, out10, 0, nullptr, take_scalar_signal());
-    return launch_ok();
-  }
-  return launch_stages<IN_TRACE>(M, I, Q, park, st, [&](const SortedPark& sp) {
-    hipLaunchKernelGGL(trace_out_kernel, grid, block, 0, st, M, I, Q, out10, sp);
-  });
+  return launch_entry<OUT_TRACE>(
+      M, I, Q, park_of<OUT_TRACE>(out10, 0), out10, 0, nullptr, st,
+      [&](dim3 grid, dim3 block, const SortedPark& sp) {
+        hipLaunchKernelGGL(trace_out_kernel, grid, block, 0, st, M, I, Q, out10, sp);
+      },
+      no_hook);
 }
 
 }  // namespace airice

@@ -10,9 +10,11 @@
 //                                                            (one 128-byte packed record per
 //                                                            interpolation pair when packed),
 //                    _Table                 (.cc:1305-1462)  interpolation in height, checks.
-//                  Lanes that hit the one-sided extrapolation case (.cc:1418) are flagged and
-//                  finished by the masked minimizer pass (launch_lookup_fallback,
-//                  airice_kernels.hip), which reproduces the reference's fallback call.
+//                  A lane that hits the one-sided extrapolation case (.cc:1418) is flagged
+//                  (AIRICE_LOOKUP_FALLBACK) and runs the reference's minimizer fallback in place:
+//                  the root finder, then stage 2 of the fallback entry point with the root in
+//                  registers (EntryPoint<OUT_FALLBACK>, airice_kernels.hip, where the kernel
+//                  lives).  A one-query call solves its fallback through launch_lookup_fallback.
 //
 // Cost model: every lane gathers its own lines, so the kernel is bound by the 128-byte lines it
 // pulls from L2 / the Infinity Cache per query, not by bytes.  With the packed copy a query reads

@@ -193,29 +193,6 @@ int folded_ice(const airice_medium* m, int variant, double ice_h, double rx_dept
   return AIRICE_OK;
 }
 
-int solve_query_host(const airice_medium* m, int variant, double ice_h, const double* in,
-                     bool has_thr, double* out, uint8_t* status) {
-  const DevMedium* M = nullptr;
-  const IceConsts* I = nullptr;
-  if (int rc = folded_ice(m, variant, ice_h, 0.0, &M, &I)) return rc;
-  return solve_host_one(*M, *I, variant, in, has_thr, out, status);
-}
-
-int hdtip_query_host(const airice_medium* m, double ice_cm, const double* in, double* out9,
-                     uint8_t* ok) {
-  const DevMedium* M = nullptr;
-  const IceConsts* I = nullptr;
-  if (int rc = folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I)) return rc;
-  return hdtip_host_one(*M, *I, ice_cm, in, out9, ok);
-}
-
-int trace_query_host(const airice_medium* m, const double* in, double* out10) {
-  const DevMedium* M = nullptr;
-  const IceConsts* I = nullptr;
-  if (int rc = folded_ice(m, AIRICE_VARIANT_PYWRAPPER, 0.0, 0.0, &M, &I)) return rc;
-  return trace_host_one(*M, *I, in, out10);
-}
-
 // ---- kernel timer (bench only) ---------------------------------------------------------
 std::atomic<bool> g_ktimer_on{false};
 static std::mutex g_kt_mu;
@@ -388,42 +365,101 @@ int ScalarCall::sync() {
   return AIRICE_OK;
 }
 
-int lookup_fallback_one(const airice_medium* m, double src_cm, double dist_cm, double depth_cm,
-                        double ice_cm, bool good, int flags, double out9[9], bool* ok) {
-  if (scalar_on_host()) {
-    const DevMedium* Mh = nullptr;
-    const IceConsts* Ih = nullptr;
-    if (int rc = folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &Mh, &Ih)) return rc;
-    const double in[3] = {src_cm, dist_cm, depth_cm};
-    uint8_t okb = good ? 1 : 0;
-    const uint8_t fl = (uint8_t)flags;
-    if (int rc = lookup_fallback_host_one(*Mh, *Ih, ice_cm, in, out9, &okb, &fl)) return rc;
-    *ok = okb != 0;
-    return AIRICE_OK;
-  }
-  DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
-  if (rc) return rc;
-  IceConsts I;
-  build_ice_consts(M, ice_cm / 100, 0.0, &I);  // as airice_table_lookup_launch
+// ---- one query of a minimizer entry point -----------------------------------------------------
+// Each *_one below runs its query on the host (the cached folds and the entry point's host route)
+// when scalar_on_host(), else on the device through the scalar slot (slot_call).
+//
+// The slot's layout, the same for every entry point: the query inputs at h[0 .. 3], the outputs
+// (ld = 1) from h[4], the flag bytes at h + 32, past the widest entry point's 17 outputs.
+// n_inline: how many of the inputs also travel in the kernel arguments (ScalarCall::arm).
+// launch(d_in, d_out, d_flag, stream) enqueues the call's one kernel on the device views.
+namespace {
+constexpr int kSlotOut = 4, kSlotFlag = 32;
+template <class Launch>
+int slot_call(const double* in, int n_in, int n_inline, double* out, int n_out, uint8_t* flag,
+              int n_flag, Launch launch) {
   ScalarCall call;
   if (!call.ok()) return AIRICE_EHIP;
-  ScalarSlot& sl = call.slot();
-  sl.h[0] = src_cm;
-  sl.h[1] = dist_cm;
-  sl.h[2] = depth_cm;
-  uint8_t* hb = reinterpret_cast<uint8_t*>(sl.h + 12);
-  hb[0] = good ? 1 : 0;
-  hb[1] = (uint8_t)flags;
-  uint8_t* db = reinterpret_cast<uint8_t*>(sl.d + 12);
-  call.arm();
-  rc = launch_lookup_fallback(M, I, sl.d, sl.d + 1, sl.d + 2, ice_cm, 1, sl.d + 3, 1, db, db + 1,
-                              sl.st);
+  ScalarSlot& s = call.slot();
+  std::copy(in, in + n_in, s.h);
+  uint8_t* flag_h = reinterpret_cast<uint8_t*>(s.h + kSlotFlag);
+  std::copy(flag, flag + n_flag, flag_h);
+  call.arm(s.h, n_inline);
+  int rc = launch(s.d, s.d + kSlotOut, reinterpret_cast<uint8_t*>(s.d + kSlotFlag), s.st);
   if (rc == AIRICE_OK) rc = call.sync();
   if (rc) return rc;
-  for (int c = 0; c < 9; ++c) out9[c] = sl.h[3 + c];
-  *ok = hb[0] != 0;
+  std::copy(s.h + kSlotOut, s.h + kSlotOut + n_out, out);
+  std::copy(flag_h, flag_h + n_flag, flag);
   return AIRICE_OK;
+}
+}  // namespace
+
+int solve_one(const airice_medium* m, int variant, double ice_h, const double in[4], bool has_thr,
+              double* out, uint8_t* status) {
+  if (scalar_on_host()) {
+    const DevMedium* M = nullptr;
+    const IceConsts* I = nullptr;
+    if (int rc = folded_ice(m, variant, ice_h, 0.0, &M, &I)) return rc;
+    return solve_host_one(*M, *I, variant, in, has_thr, out, status);
+  }
+  const int fields = variant == AIRICE_VARIANT_PYWRAPPER ? AIRICE_PYSOLVE_FIELDS : AIRICE_SOLVE_FIELDS;
+  return slot_call(in, 4, has_thr ? 4 : 3, out, fields, status, status != nullptr ? 1 : 0,
+                   [&](const double* d, double* o, uint8_t* f, hipStream_t st) {
+                     return airice_solve_launch(m, variant, ice_h, d, d + 1, d + 2,
+                                                has_thr ? d + 3 : nullptr, 1, o, 1,
+                                                status != nullptr ? f : nullptr, st);
+                   });
+}
+
+int hdtip_one(const airice_medium* m, double ice_cm, const double in[3], double out9[9],
+              uint8_t* ok) {
+  if (scalar_on_host()) {
+    const DevMedium* M = nullptr;
+    const IceConsts* I = nullptr;
+    if (int rc = folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I)) return rc;
+    return hdtip_host_one(*M, *I, ice_cm, in, out9, ok);
+  }
+  return slot_call(in, 3, 3, out9, 9, ok, 1,
+                   [&](const double* d, double* o, uint8_t* f, hipStream_t st) {
+                     return airice_hdtip_launch(m, d, d + 1, d + 2, ice_cm, 1, o, 1, f, st);
+                   });
+}
+
+int trace_one(const airice_medium* m, const double in[4], double out10[10]) {
+  if (scalar_on_host()) {
+    const DevMedium* M = nullptr;
+    const IceConsts* I = nullptr;
+    if (int rc = folded_ice(m, AIRICE_VARIANT_PYWRAPPER, 0.0, 0.0, &M, &I)) return rc;
+    return trace_host_one(*M, *I, in, out10);
+  }
+  return slot_call(in, 4, 4, out10, 10, nullptr, 0,
+                   [&](const double* d, double* o, uint8_t*, hipStream_t st) {
+                     return airice_trace_ice_to_air_launch(m, d, d + 1, d + 2, d + 3, 1, o, st);
+                   });
+}
+
+int lookup_fallback_one(const airice_medium* m, double src_cm, double dist_cm, double depth_cm,
+                        double ice_cm, bool good, int flags, double out9[9], bool* ok) {
+  const double in[3] = {src_cm, dist_cm, depth_cm};
+  uint8_t fb[2] = {(uint8_t)(good ? 1 : 0), (uint8_t)flags};  // the ok byte, the lookup's flags
+  int rc;
+  if (scalar_on_host()) {
+    const DevMedium* M = nullptr;
+    const IceConsts* I = nullptr;
+    if ((rc = folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I))) return rc;
+    rc = lookup_fallback_host_one(*M, *I, ice_cm, in, out9, &fb[0], &fb[1]);
+  } else {
+    rc = slot_call(in, 3, 0, out9, 9, fb, 2,
+                   [&](const double* d, double* o, uint8_t* f, hipStream_t st) {
+                     DevMedium M;
+                     if (int rm = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M)) return rm;
+                     IceConsts I;
+                     build_ice_consts(M, ice_cm / 100, 0.0, &I);  // as airice_table_lookup_launch
+                     return launch_lookup_fallback(M, I, d, d + 1, d + 2, ice_cm, o, 1, f, f + 1, st);
+                   });
+  }
+  if (rc == AIRICE_OK) *ok = fb[0] != 0;
+  return rc;
 }
 
 }  // namespace airice
@@ -695,8 +731,7 @@ int airice_solve_host(const airice_medium* m, int variant, double ice_h_m, const
                           straight_angle != nullptr ? straight_angle[0] : 0.0};
     double o[AIRICE_SOLVE_FIELDS];
     uint8_t st = 0;
-    if (int rc = airice::solve_query_host(m, variant, ice_h_m, in, straight_angle != nullptr, o,
-                                          &st))
+    if (int rc = airice::solve_one(m, variant, ice_h_m, in, straight_angle != nullptr, o, &st))
       return rc;
     for (int c = 0; c < fields; ++c) out[(size_t)c * ld] = o[c];
     if (status) status[0] = st;
@@ -1033,7 +1068,7 @@ int airice_trace_ice_to_air_host(const airice_medium* m, const double* depth, co
   }
   if (n == 1 && airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
     const double in[4] = {depth[0], ice[0], txh[0], dist[0]};
-    return airice::trace_query_host(m, in, out10);
+    return airice::trace_one(m, in, out10);
   }
   DevBuffer mem;
   HIP_TRY(mem.alloc(sizeof(double) * 14 * n));

@@ -371,30 +371,14 @@ double MinimizeforLaunchAngle(double x, void* params) {
                  {x, p->airtxheight, p->icelayerheight, p->antennadepth, p->horizontaldistance});
 }
 
-// ---- one-query solves: one launch chain through the scalar slot ----------------------------
+// ---- one-query solves (airice::solve_one / hdtip_one: on the host, or through the scalar slot) --
 void Air2IceRayTracing(double AirTxHeight, double HorizontalDistance, double IceLayerHeight,
                        double AntennaDepth, double StraightAngle, double dummy[20]) {
   const airice_medium m = medium();
-  if (airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
-    const double in[4] = {AirTxHeight, HorizontalDistance, AntennaDepth, StraightAngle};
-    if (airice::solve_query_host(&m, AIRICE_VARIANT_MULTIRAY, IceLayerHeight, in, true, dummy,
-                                 nullptr) != AIRICE_OK)
-      die("Air2IceRayTracing");
-    return;
-  }
-  airice::ScalarCall call;
-  if (!call.ok()) die("Air2IceRayTracing");
-  airice::ScalarSlot& s = call.slot();
-  s.h[0] = AirTxHeight;
-  s.h[1] = HorizontalDistance;
-  s.h[2] = AntennaDepth;
-  s.h[3] = StraightAngle;
-  call.arm(s.h, 4);
-  if (airice_solve_launch(&m, AIRICE_VARIANT_MULTIRAY, IceLayerHeight, s.d, s.d + 1, s.d + 2,
-                          s.d + 3, 1, s.d + 4, 1, nullptr, s.st) != AIRICE_OK ||
-      call.sync() != AIRICE_OK)
+  const double in[4] = {AirTxHeight, HorizontalDistance, AntennaDepth, StraightAngle};
+  if (airice::solve_one(&m, AIRICE_VARIANT_MULTIRAY, IceLayerHeight, in, true, dummy, nullptr) !=
+      AIRICE_OK)
     die("Air2IceRayTracing");
-  std::memcpy(dummy, s.h + 4, sizeof(double) * AIRICE_SOLVE_FIELDS);
 }
 
 void GetRayTracingSolutions(double RayLaunchAngleInAir, double AirTxHeight, double IceLayerHeight,
@@ -426,37 +410,11 @@ bool GetHorizontalDistanceToIntersectionPoint(
     double& horizontalDistanceToIntersectionPoint, double& transmissionCoefficientS,
     double& transmissionCoefficientP, double& RecievedAngleInIce) {
   const airice_medium m = medium();
-  if (airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
-    const double in[3] = {SrcHeightASL, HorizontalDistanceToRx, RxDepthBelowIceBoundary};
-    double o[9];
-    uint8_t ok = 0;
-    if (airice::hdtip_query_host(&m, IceLayerHeight, in, o, &ok) != AIRICE_OK)
-      die("GetHorizontalDistanceToIntersectionPoint");
-    opticalPathLengthInIce = o[0];
-    opticalPathLengthInAir = o[1];
-    geometricalPathLengthInIce = o[2];
-    geometricalPathLengthInAir = o[3];
-    launchAngle = o[4];
-    horizontalDistanceToIntersectionPoint = o[5];
-    transmissionCoefficientS = o[6];
-    transmissionCoefficientP = o[7];
-    RecievedAngleInIce = o[8];
-    return ok != 0;
-  }
-  airice::ScalarCall call;
-  if (!call.ok()) die("GetHorizontalDistanceToIntersectionPoint");
-  airice::ScalarSlot& s = call.slot();
-  s.h[0] = SrcHeightASL;
-  s.h[1] = HorizontalDistanceToRx;
-  s.h[2] = RxDepthBelowIceBoundary;
-  uint8_t* ok_h = reinterpret_cast<uint8_t*>(s.h + 12);
-  uint8_t* ok_d = reinterpret_cast<uint8_t*>(s.d + 12);
-  call.arm(s.h, 3);
-  if (airice_hdtip_launch(&m, s.d, s.d + 1, s.d + 2, IceLayerHeight, 1, s.d + 3, 1, ok_d, s.st) !=
-          AIRICE_OK ||
-      call.sync() != AIRICE_OK)
+  const double in[3] = {SrcHeightASL, HorizontalDistanceToRx, RxDepthBelowIceBoundary};
+  double o[9];
+  uint8_t ok = 0;
+  if (airice::hdtip_one(&m, IceLayerHeight, in, o, &ok) != AIRICE_OK)
     die("GetHorizontalDistanceToIntersectionPoint");
-  const double* o = s.h + 3;
   opticalPathLengthInIce = o[0];
   opticalPathLengthInAir = o[1];
   geometricalPathLengthInIce = o[2];
@@ -466,7 +424,7 @@ bool GetHorizontalDistanceToIntersectionPoint(
   transmissionCoefficientS = o[6];
   transmissionCoefficientP = o[7];
   RecievedAngleInIce = o[8];
-  return ok_h[0] != 0;
+  return ok != 0;
 }
 
 // ---- MakeRayTracingTable (.cc:2019-2158) ---------------------------------------------------

@@ -156,30 +156,13 @@ int layer_of(double zabs) {  // GetB_air / GetC_air layer scan (.cc:180-189)
   return which;
 }
 
-// one launch-angle solve through the scalar slot: dummy[0..14] (.cc:1070-1084), status bits
+// one launch-angle solve (airice::solve_one): dummy[0..14] (.cc:1070-1084)
 void solve_one(const airice_medium& m, double H, double D, double ice, double depth,
                const double* straight_angle, double dummy[AIRICE_PYSOLVE_FIELDS]) {
-  if (airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
-    const double in[4] = {H, D, depth, straight_angle != nullptr ? *straight_angle : 0.0};
-    if (airice::solve_query_host(&m, AIRICE_VARIANT_PYWRAPPER, ice, in, straight_angle != nullptr,
-                                 dummy, nullptr) != AIRICE_OK)
-      die("Air2IceRayTracing");
-    return;
-  }
-  airice::ScalarCall call;
-  if (!call.ok()) die("Air2IceRayTracing");
-  airice::ScalarSlot& s = call.slot();
-  s.h[0] = H;
-  s.h[1] = D;
-  s.h[2] = depth;
-  s.h[3] = straight_angle != nullptr ? *straight_angle : 0.0;
-  call.arm(s.h, straight_angle != nullptr ? 4 : 3);
-  if (airice_solve_launch(&m, AIRICE_VARIANT_PYWRAPPER, ice, s.d, s.d + 1, s.d + 2,
-                          straight_angle != nullptr ? s.d + 3 : nullptr, 1, s.d + 4, 1, nullptr,
-                          s.st) != AIRICE_OK ||
-      call.sync() != AIRICE_OK)
+  const double in[4] = {H, D, depth, straight_angle != nullptr ? *straight_angle : 0.0};
+  if (airice::solve_one(&m, AIRICE_VARIANT_PYWRAPPER, ice, in, straight_angle != nullptr, dummy,
+                        nullptr) != AIRICE_OK)
     die("Air2IceRayTracing");
-  std::memcpy(dummy, s.h + 4, sizeof(double) * AIRICE_PYSOLVE_FIELDS);
 }
 
 }  // namespace
@@ -390,25 +373,9 @@ void TraceIceToAir(double AntennaDepth, double IceLayerHeight, double AirTxHeigh
     m = medium();
   }
   // GetRayTracingSolution + the launch/receive swap + ArrayParameters (TraceIceToAir.C:27-68):
-  // one launch of the batch trace path with n = 1
-  if (airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
-    const double in[4] = {AntennaDepth, IceLayerHeight, AirTxHeight, HorizontalDistance};
-    if (airice::trace_query_host(&m, in, ArrayParameters) != AIRICE_OK) die("TraceIceToAir");
-  } else {
-    airice::ScalarCall call;
-    if (!call.ok()) die("TraceIceToAir");
-    airice::ScalarSlot& s = call.slot();
-    s.h[0] = AntennaDepth;
-    s.h[1] = IceLayerHeight;
-    s.h[2] = AirTxHeight;
-    s.h[3] = HorizontalDistance;
-    call.arm(s.h, 4);
-    if (airice_trace_ice_to_air_launch(&m, s.d, s.d + 1, s.d + 2, s.d + 3, 1, s.d + 4, s.st) !=
-            AIRICE_OK ||
-        call.sync() != AIRICE_OK)
-      die("TraceIceToAir");
-    std::memcpy(ArrayParameters, s.h + 4, sizeof(double) * 10);
-  }
+  // the batch trace path with n = 1
+  const double in[4] = {AntennaDepth, IceLayerHeight, AirTxHeight, HorizontalDistance};
+  if (airice::trace_one(&m, in, ArrayParameters) != AIRICE_OK) die("TraceIceToAir");
   static const bool verbose = [] {
     const char* v = std::getenv("AIRICE_VERBOSE");
     return v != nullptr && std::strcmp(v, "1") == 0;
