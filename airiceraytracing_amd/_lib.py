@@ -141,6 +141,7 @@ SINGLE_RAY_WORK = 32   # AIRICE_SINGLE_RAY_WORK
 
 LOOKUP_FALLBACK = 1  # AIRICE_LOOKUP_FALLBACK
 LOOKUP_UNPINNED = 2  # AIRICE_LOOKUP_UNPINNED
+LOOKUP_MAX_TABLES = 32  # AIRICE_LOOKUP_MAX_TABLES
 
 # Every symbol include/airice.h declares (checked by tests/test_capi.py).
 # RayTracingFunctions:: scalar ops (include/airice.h AIRICE_RTF_*)
@@ -156,7 +157,8 @@ EXPORTED_SYMBOLS = (
     "airice_nz_air", "airice_nz_ice", "airice_grid_init", "airice_table_launch",
     "airice_table_launch_multi",
     "airice_table_host", "airice_rays_launch", "airice_rays_host", "airice_scalar_mode", "airice_solve_launch", "airice_solve_host",
-    "airice_hdtip_launch", "airice_table_lookup_launch", "airice_lookup_pack", "airice_lookup_pack_floats", "airice_single_ray_plan",
+    "airice_hdtip_launch", "airice_table_lookup_launch",
+    "airice_table_lookup_multi_work_bytes", "airice_table_lookup_launch_multi", "airice_lookup_pack", "airice_lookup_pack_floats", "airice_single_ray_plan",
     "airice_single_ray_launch", "airice_single_ray_host", "airice_ray_paths_plan",
     "airice_ray_paths_launch", "airice_ray_paths_host", "airice_trace_ice_to_air_launch",
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
@@ -222,6 +224,10 @@ def lib() -> ctypes.CDLL:
         "airice_hdtip_launch": ([M, P, P, P, D, S, P, S, P, P], I),
         "airice_table_lookup_launch": ([M, ctypes.POINTER(LookupTable), P, P, P, D, S, P, S, P,
                                         P, P], I),
+        "airice_table_lookup_multi_work_bytes": ([ctypes.c_int32, ctypes.c_int32], S),
+        "airice_table_lookup_launch_multi": ([M, ctypes.POINTER(LookupTable), ctypes.c_int32, P, P,
+                                              ctypes.c_int32, P, P, S, D, S, P, S, P, P, P, S, P],
+                                             I),
         "airice_lookup_pack": ([ctypes.POINTER(LookupTable), P, S, P], I),
         "airice_lookup_pack_floats": ([S, ctypes.c_int32], S),
         "airice_single_ray_plan": ([M, D, D, D, D, ctypes.POINTER(SingleRayInfo)], I),

@@ -54,6 +54,15 @@ size_t group_min_batch(int in);
 int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_table* t,
                   const double* src, const double* dist, const double* depth, double ice_cm,
                   size_t n, double* out, size_t ld, uint8_t* ok, uint8_t* flags, hipStream_t st);
+// The same for n_ant antennas x n_src sources in ONE launch (lookup_multi_kernel): the tables'
+// descriptions and each antenna's (table, Rx depth) are uploaded into d_work
+// (lookup_multi_work_bytes), no allocation.  The caller has validated every argument.
+size_t lookup_multi_work_bytes(size_t n_tables, size_t n_ant);
+int launch_lookup_multi(const DevMedium& M, const IceConsts& I, const airice_lookup_table* tables,
+                        int n_tables, const int32_t* antenna_table, const double* antenna_depth_cm,
+                        size_t n_ant, const double* src, const double* dist, size_t ld_dist,
+                        double ice_cm, size_t n_src, double* out, size_t ld, uint8_t* ok,
+                        uint8_t* flags, void* d_work, hipStream_t st);
 int launch_lookup_pack(const airice_lookup_table* t, float* entries, hipStream_t st);
 // the lookup's fallback for one query on the device (batches solve theirs in lookup_kernel)
 int launch_lookup_fallback(const DevMedium& M, const IceConsts& I, const double* src,
@@ -153,6 +162,7 @@ enum KTimerId {
   KT_LOOKUP,
   KT_RAY_CONSTS,
   KT_RAY_PATHS,
+  KT_LOOKUP_MULTI,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -179,6 +189,7 @@ enum LaunchId {
   LC_PATH,          // path_kernel
   LC_RAY_CONSTS,    // ray_consts_kernel
   LC_RAY_PATHS,     // ray_paths_kernel
+  LC_LOOKUP_MULTI,  // lookup_multi_kernel
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

@@ -24,6 +24,8 @@
 //  scalar_solve_kernel<IN, OUT> : one query (n = 1), both stages in one launch on one wave.
 //  lookup_kernel        : the table lookup (.cc:1305-1462, airice_lookup.hpp); a lane that needs
 //                         the reference's minimizer fallback solves it in place.
+//  lookup_multi_kernel  : the same lookup for many antennas x many sources in one launch, one
+//                         antenna per block, its table's description read through scalar loads.
 //
 // Data layout in HBM: structure-of-arrays, column c of item i at out[c*ld + i], so each
 // wave's store of one column is one contiguous 256 B (f32) / 512 B (f64) segment.
@@ -2994,19 +2996,21 @@ int launch_lookup_fallback(const DevMedium& M, const IceConsts& I, const double*
 // chunks, flagged lanes listed in LDS -- waited for the whole launch and then for one solve's
 // latency: 100.8-101.8 against 93.1-93.5 us per 1e6 random queries, same outputs.)
 // 128 VGPRs (the root finder's cap, 4 waves/SIMD as the lookup alone at 97).
-__global__ __launch_bounds__(kLkBlock, kRootsWaves) void lookup_kernel(
-    LkTable T, DevMedium M, IceConsts I, QueryArgs Q, double* __restrict__ out, size_t ld,
-    uint8_t* __restrict__ ok, uint8_t* __restrict__ flags, int exact) {
-  const long long k = (long long)blockIdx.x * kLkBlock + threadIdx.x;
-  if (k >= Q.n) return;
+// One lane's query of the two lookup kernels.  Q: the lane's own source height, distance and Rx
+// depth at index 0 (cm), Q.ice the fallback's ice argument; k: the query's slot in out / ok /
+// flags; win: the lane's column of the block's LDS window.
+__device__ __forceinline__ void lookup_lane(LkTable T, const DevMedium& M, const IceConsts& I,
+                                            const QueryArgs& Q, double* __restrict__ out,
+                                            size_t ld, uint8_t* __restrict__ ok,
+                                            uint8_t* __restrict__ flags, long long k, int exact,
+                                            float* win) {
   if (T.ang != nullptr && *reinterpret_cast<const int*>(T.ang + (lk_angles_ok_offset(T.n, T.asteps) -
                                                                   lk_angles_offset(T.n, T.asteps))) == 0)
     T.ang = nullptr;
-  __shared__ float s_win[kLkWindow][kLkBlock];
   int fl = 0;
   double o[9];
   bool good = false;
-  const bool fb = lk_query(T, Q.a[k] / 100, Q.b[k] / 100, M.d2r, o, &good, fl, &s_win[0][threadIdx.x]);
+  const bool fb = lk_query(T, Q.a[0] / 100, Q.b[0] / 100, M.d2r, o, &good, fl, win);
   if (!fb) {
 #pragma unroll
     for (int c = 0; c < 9; ++c) __builtin_nontemporal_store(o[c], out + c * ld + k);
@@ -3015,11 +3019,78 @@ __global__ __launch_bounds__(kLkBlock, kRootsWaves) void lookup_kernel(
   flags[k] = (uint8_t)fl;
   if (fb) {
     double thR;
-    const Geometry g = load_query<IN_CM100>(M, Q, k, thR);
+    const Geometry g = load_query<IN_CM100>(M, Q, 0, thR);
     const SolveResult r = solve_root(M, I, g, thR, exact != 0, &kLogTable[0][0]);
     stage2_out<OUT_FALLBACK, AT_DIRECT>(M, I, Q, out, ld, ok, k, &kLogTable[0][0],
                                         WaveRoot{r.root, r.status, g});
   }
+}
+
+__global__ __launch_bounds__(kLkBlock, kRootsWaves) void lookup_kernel(
+    LkTable T, DevMedium M, IceConsts I, QueryArgs Q, double* __restrict__ out, size_t ld,
+    uint8_t* __restrict__ ok, uint8_t* __restrict__ flags, int exact) {
+  const long long k = (long long)blockIdx.x * kLkBlock + threadIdx.x;
+  if (k >= Q.n) return;
+  __shared__ float s_win[kLkWindow][kLkBlock];
+  const QueryArgs q{Q.a + k, Q.b + k, Q.c + k, nullptr, Q.ice, 1, nullptr};
+  lookup_lane(T, M, I, q, out, ld, ok, flags, k, exact, &s_win[0][threadIdx.x]);
+}
+
+// The same lookup for n_ant antennas x n_src sources in one launch: every lane of a block works
+// for one antenna (blockIdx.y, .z), so the antenna's record and its table's description are
+// block-uniform and come through scalar loads from the workspace the launcher filled (tabs: the
+// distinct tables, ants: each antenna's table and Rx depth).  Lane i of antenna a reads src[i] and
+// dist[a * ld_dist + i] and writes slot a * n_src + i: lookup_lane, the bits of one lookup_kernel
+// launch per antenna.
+struct LkAntenna {
+  double depth_cm;
+  int table;
+  int pad_;
+};
+// LkTable as the kernel reads it from the workspace: the same layout with the pointers typed as
+// global memory.  (A pointer that is read from memory is generic to the compiler -- flat loads,
+// which wait on the LDS counter too; typed like this the gathers are global loads as in
+// lookup_kernel, whose pointers are kernel arguments.)
+typedef const __attribute__((address_space(1))) float* LkGlobalPtr;
+struct LkTableDev {
+  LkGlobalPtr col[AIRICE_TABLE_COLUMNS];
+  LkGlobalPtr e;
+  long long n;
+  double stop_h, step_h;
+  int hsteps, asteps;
+  long long rows;
+  LkGlobalPtr ang;
+};
+static_assert(sizeof(LkTableDev) == sizeof(LkTable) &&
+                  offsetof(LkTableDev, ang) == offsetof(LkTable, ang) &&
+                  offsetof(LkTableDev, n) == offsetof(LkTable, n),
+              "the launcher uploads LkTable images");
+
+__global__ __launch_bounds__(kLkBlock, kRootsWaves) void lookup_multi_kernel(
+    const LkTableDev* __restrict__ tabs, const LkAntenna* __restrict__ ants, int n_ant, DevMedium M,
+    IceConsts I, const double* __restrict__ src, const double* __restrict__ dist, size_t ld_dist,
+    double ice, long long n_src, double* __restrict__ out, size_t ld, uint8_t* __restrict__ ok,
+    uint8_t* __restrict__ flags, int exact) {
+  const long long a = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+  const long long i = (long long)blockIdx.x * kLkBlock + threadIdx.x;
+  if (a >= n_ant || i >= n_src) return;
+  const LkAntenna* A = ants + a;
+  __shared__ float s_win[kLkWindow][kLkBlock];
+  const QueryArgs q{src + i, dist + a * ld_dist + i, &A->depth_cm, nullptr, ice, 1, nullptr};
+  const LkTableDev* Tp = tabs + A->table;
+  LkTable T;
+#pragma unroll
+  for (int c = 0; c < AIRICE_TABLE_COLUMNS; ++c) T.col[c] = (const float*)Tp->col[c];
+  T.e = (const float*)Tp->e;
+  T.n = Tp->n;
+  T.stop_h = Tp->stop_h;
+  T.step_h = Tp->step_h;
+  T.hsteps = Tp->hsteps;
+  T.asteps = Tp->asteps;
+  T.rows = Tp->rows;
+  T.ang = (const float*)Tp->ang;
+  lookup_lane(T, M, I, q, out, ld, ok, flags, a * n_src + i, exact,
+              &s_win[0][threadIdx.x]);
 }
 
 int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_table* t,
@@ -3034,6 +3105,42 @@ int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_ta
   hipLaunchKernelGGL(lookup_kernel, dim3(grid), dim3(kLkBlock), 0, st, T, M, I, Q, out, ld, ok,
                      flags, bisect_exact());
   ktimer_end(KT_LOOKUP, st);
+  return launch_ok();
+}
+
+size_t lookup_multi_work_bytes(size_t n_tables, size_t n_ant) {
+  return (n_tables * sizeof(LkTable) + n_ant * sizeof(LkAntenna) + 15) / 16 * 16;
+}
+
+int launch_lookup_multi(const DevMedium& M, const IceConsts& I, const airice_lookup_table* tables,
+                        int n_tables, const int32_t* antenna_table, const double* antenna_depth_cm,
+                        size_t n_ant, const double* src, const double* dist, size_t ld_dist,
+                        double ice_cm, size_t n_src, double* out, size_t ld, uint8_t* ok,
+                        uint8_t* flags, void* d_work, hipStream_t st) {
+  if (n_ant == 0 || n_src == 0) return AIRICE_OK;
+  // the staging image of the workspace: the tables' descriptions, then the antennas' records
+  const size_t tab_bytes = (size_t)n_tables * sizeof(LkTable);
+  std::vector<char> img(tab_bytes + n_ant * sizeof(LkAntenna));
+  LkTable* ht = reinterpret_cast<LkTable*>(img.data());
+  LkAntenna* ha = reinterpret_cast<LkAntenna*>(img.data() + tab_bytes);
+  for (int t = 0; t < n_tables; ++t) ht[t] = lk_table(tables + t);
+  for (size_t a = 0; a < n_ant; ++a) ha[a] = LkAntenna{antenna_depth_cm[a], antenna_table[a], 0};
+  // (a copy from pageable memory returns once the source has been read)
+  if (hipMemcpyAsync(d_work, img.data(), img.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+    return AIRICE_EHIP;
+  const LkTableDev* d_tabs = static_cast<const LkTableDev*>(d_work);
+  const LkAntenna* d_ants =
+      reinterpret_cast<const LkAntenna*>(static_cast<const char*>(d_work) + tab_bytes);
+  constexpr size_t kMaxY = 65535;
+  const unsigned gy = (unsigned)(n_ant < kMaxY ? n_ant : kMaxY);
+  const dim3 grid((unsigned)((n_src + kLkBlock - 1) / kLkBlock), gy,
+                  (unsigned)((n_ant + gy - 1) / gy));
+  ktimer_begin(KT_LOOKUP_MULTI, st);
+  count_launch(LC_LOOKUP_MULTI);
+  hipLaunchKernelGGL(lookup_multi_kernel, grid, dim3(kLkBlock), 0, st, d_tabs, d_ants, (int)n_ant,
+                     M, I, src, dist, ld_dist, fallback_ice_arg(ice_cm), (long long)n_src, out, ld,
+                     ok, flags, bisect_exact());
+  ktimer_end(KT_LOOKUP_MULTI, st);
   return launch_ok();
 }
 

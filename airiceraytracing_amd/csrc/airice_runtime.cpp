@@ -205,13 +205,14 @@ static KtPair g_kt_open[KT_COUNT];                // pair whose end is pending
 static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kernel",
                                                "group_passes",      "out_kernel",
                                                "lookup_kernel",     "ray_consts_kernel",
-                                               "ray_paths_kernel"};
+                                               "ray_paths_kernel",  "lookup_multi_kernel"};
 
 std::atomic<long long> g_launches[LC_COUNT];
 static const char* const kLcNames[LC_COUNT] = {
     "table_kernel",        "rays_kernel",  "scalar_ray_kernel", "roots_kernel",
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
-    "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel"};
+    "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
+    "lookup_multi_kernel"};
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
 // them from a child process).
@@ -802,6 +803,84 @@ int airice_table_lookup_launch(const airice_medium* m, const airice_lookup_table
   rc = launch_lookup(M, I, t, d_src_cm, d_dist_cm, d_depth_cm, ice_cm, n, d_out, ld, d_ok,
                      d_flags, (hipStream_t)stream);
   if (rc) set_error("lookup launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
+
+size_t airice_table_lookup_multi_work_bytes(int32_t n_tables, int32_t n_ant) {
+  if (n_tables < 1 || n_tables > AIRICE_LOOKUP_MAX_TABLES || n_ant < 0) return 0;
+  return airice::lookup_multi_work_bytes((size_t)n_tables, (size_t)n_ant);
+}
+
+int airice_table_lookup_launch_multi(const airice_medium* m, const airice_lookup_table* tables,
+                                     int32_t n_tables, const int32_t* antenna_table,
+                                     const double* antenna_depth_cm, int32_t n_ant,
+                                     const double* d_src_cm, const double* d_dist_cm,
+                                     size_t ld_dist, double ice_cm, size_t n_src, double* d_out,
+                                     size_t ld, uint8_t* d_ok, uint8_t* d_flags, void* d_work,
+                                     size_t work_bytes, void* stream) {
+  if (n_tables < 1 || n_tables > AIRICE_LOOKUP_MAX_TABLES) {
+    set_error("lookup multi: n_tables = %d outside 1..%d", n_tables, AIRICE_LOOKUP_MAX_TABLES);
+    return AIRICE_EINVAL;
+  }
+  if (n_ant < 0) {
+    set_error("lookup multi: n_ant = %d", n_ant);
+    return AIRICE_EINVAL;
+  }
+  const bool work = n_ant > 0 && n_src > 0;
+  if (m == nullptr || tables == nullptr ||
+      (n_ant > 0 && (antenna_table == nullptr || antenna_depth_cm == nullptr)) ||
+      (work && (d_src_cm == nullptr || d_dist_cm == nullptr || d_out == nullptr ||
+                d_ok == nullptr || d_flags == nullptr || d_work == nullptr))) {
+    set_error("lookup multi: null argument");
+    return AIRICE_EINVAL;
+  }
+  for (int32_t i = 0; i < n_tables; ++i) {
+    const airice_lookup_table* t = tables + i;
+    if (t->table == nullptr) {
+      set_error("lookup multi: null argument (tables[%d].table)", i);
+      return AIRICE_EINVAL;
+    }
+    if (t->n_entries == 0 || t->ld < t->n_entries || t->total_angle_steps < 1 ||
+        t->total_height_steps < 1 || !(t->height_step > 0) ||
+        (reinterpret_cast<uintptr_t>(t->entries) & 15) != 0) {
+      set_error("lookup multi: invalid lookup table description (tables[%d])", i);
+      return AIRICE_EINVAL;
+    }
+  }
+  for (int32_t a = 0; a < n_ant; ++a)
+    if (antenna_table[a] < 0 || antenna_table[a] >= n_tables) {
+      set_error("lookup multi: antenna_table[%d] = %d outside [0, %d)", a, antenna_table[a],
+                n_tables);
+      return AIRICE_EINVAL;
+    }
+  if (ld_dist < n_src) {
+    set_error("lookup multi: ld_dist (%zu) < n_src (%zu)", ld_dist, n_src);
+    return AIRICE_EINVAL;
+  }
+  if (n_src >= (1ull << 32)) {
+    set_error("lookup multi: n_src = %zu exceeds one launch", n_src);
+    return AIRICE_EINVAL;
+  }
+  if (ld < (size_t)n_ant * n_src) {
+    set_error("lookup multi: ld (%zu) < n_ant*n_src (%zu)", ld, (size_t)n_ant * n_src);
+    return AIRICE_EINVAL;
+  }
+  if (!work) return AIRICE_OK;
+  const size_t need = airice::lookup_multi_work_bytes((size_t)n_tables, (size_t)n_ant);
+  if (work_bytes < need || (reinterpret_cast<uintptr_t>(d_work) & 15) != 0) {
+    set_error("lookup multi: workspace of %zu bytes (16-byte aligned), need %zu "
+              "(airice_table_lookup_multi_work_bytes)", work_bytes, need);
+    return AIRICE_EINVAL;
+  }
+  DevMedium M;
+  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
+  if (rc) return rc;
+  IceConsts I;
+  build_ice_consts(M, ice_cm / 100, 0.0, &I);  // as airice_table_lookup_launch
+  rc = launch_lookup_multi(M, I, tables, n_tables, antenna_table, antenna_depth_cm, (size_t)n_ant,
+                           d_src_cm, d_dist_cm, ld_dist, ice_cm, n_src, d_out, ld, d_ok, d_flags,
+                           d_work, (hipStream_t)stream);
+  if (rc) set_error("lookup multi launch failed: %s", hipGetErrorString(hipGetLastError()));
   return rc;
 }
 

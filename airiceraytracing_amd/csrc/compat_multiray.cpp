@@ -638,14 +638,9 @@ bool GetHorizontalDistanceToIntersectionPoint_Table(
                      transmissionCoefficientP, RecievedAngleInIce);
 }
 
-void TableLookupBatch(const double* SrcHeightASL, const double* HorizontalDistanceToRx,
-                      const double* RxDepthBelowIceBoundary, double IceLayerHeight, int TableIndex,
-                      size_t n, double* out9, bool* ok) {
-  const airice_medium m = medium();
-  const std::vector<std::vector<float>>& cols = host_table(TableIndex);
-  set_minmax(cols);
-  if (n == 0) return;
-  std::lock_guard<std::mutex> lock(g_mu);
+// The description of table TableIndex's resident HBM copy with its packed copy, for the batch
+// lookups (g_mu held): the grid globals of the last table made (.cc:1035-1039).
+static airice_lookup_table packed_device_table(int TableIndex) {
   DevTable& dt = device_table(TableIndex);
   const size_t entries = dt.n;
   airice_lookup_table t;
@@ -671,6 +666,18 @@ void TableLookupBatch(const double* SrcHeightASL, const double* HorizontalDistan
     dt.packed_asteps = t.total_angle_steps;
   }
   t.entries = dt.packed;
+  return t;
+}
+
+void TableLookupBatch(const double* SrcHeightASL, const double* HorizontalDistanceToRx,
+                      const double* RxDepthBelowIceBoundary, double IceLayerHeight, int TableIndex,
+                      size_t n, double* out9, bool* ok) {
+  const airice_medium m = medium();
+  const std::vector<std::vector<float>>& cols = host_table(TableIndex);
+  set_minmax(cols);
+  if (n == 0) return;
+  std::lock_guard<std::mutex> lock(g_mu);
+  const airice_lookup_table t = packed_device_table(TableIndex);
   // one device block: src | dist | depth | out (9 columns) | ok | flags
   void* mem = nullptr;
   if (hipMalloc(&mem, sizeof(double) * 12 * n + 2 * n) != hipSuccess) die("hipMalloc");
@@ -690,6 +697,71 @@ void TableLookupBatch(const double* SrcHeightASL, const double* HorizontalDistan
   std::vector<uint8_t> hok(n);
   if (hipMemcpy(soa.data(), d + 3 * n, sizeof(double) * 9 * n, hipMemcpyDeviceToHost) !=
           hipSuccess ||
+      hipMemcpy(hok.data(), dok, n, hipMemcpyDeviceToHost) != hipSuccess)
+    die("hipMemcpy");
+  (void)hipFree(mem);
+  for (size_t i = 0; i < n; ++i) {
+    for (int c = 0; c < 9; ++c) out9[i * 9 + c] = soa[(size_t)c * n + i];
+    ok[i] = hok[i] != 0;
+  }
+}
+
+void TableLookupBatchMulti(const double* SrcHeightASL, const double* HorizontalDistanceToRx,
+                           const double* RxDepthBelowIceBoundary, double IceLayerHeight,
+                           const int* AntennaNumbers, size_t n_ant, size_t n_src, double* out9,
+                           bool* ok) {
+  const airice_medium m = medium();
+  // antenna -> table remap over the caller's vectors (.cc:1348-1352), then the distinct tables
+  std::vector<int32_t> slot(n_ant);
+  std::vector<int> used;
+  for (size_t a = 0; a < n_ant; ++a) {
+    int ant = AntennaNumbers[a];
+    if (&AntennaDepths != nullptr && &AntennaTableAlreadyMade != nullptr) {
+      for (int j = 0; j < (int)AntennaTableAlreadyMade.size(); j++)
+        if (AntennaDepths[ant] == AntennaDepths[AntennaTableAlreadyMade[j]]) ant = j;
+    }
+    size_t u = 0;
+    while (u < used.size() && used[u] != ant) ++u;
+    if (u == used.size()) {
+      set_minmax(host_table(ant));
+      used.push_back(ant);
+    }
+    slot[a] = (int32_t)u;
+  }
+  if (n_ant == 0 || n_src == 0) return;
+  if (used.size() > AIRICE_LOOKUP_MAX_TABLES || n_ant > (size_t)INT32_MAX) {
+    std::fprintf(stderr, "MultiRayAirIceRefraction: TableLookupBatchMulti: %zu antennas on %zu "
+                 "tables (at most %d tables a call)\n", n_ant, used.size(),
+                 AIRICE_LOOKUP_MAX_TABLES);
+    std::abort();
+  }
+  std::lock_guard<std::mutex> lock(g_mu);
+  std::vector<airice_lookup_table> tables;
+  for (int ti : used) tables.push_back(packed_device_table(ti));
+  const size_t n = n_ant * n_src;
+  const size_t work = airice_table_lookup_multi_work_bytes((int32_t)tables.size(), (int32_t)n_ant);
+  // one device block: workspace (a multiple of 16 bytes) | src | dist (n_ant rows) | out (9
+  // columns) | ok | flags
+  void* mem = nullptr;
+  if (hipMalloc(&mem, work + sizeof(double) * (n_src + 10 * n) + 2 * n) != hipSuccess)
+    die("hipMalloc");
+  double* dsrc = reinterpret_cast<double*>(static_cast<char*>(mem) + work);
+  double* ddist = dsrc + n_src;
+  double* dout = ddist + n;
+  uint8_t* dok = reinterpret_cast<uint8_t*>(dout + 9 * n);
+  uint8_t* dfl = dok + n;
+  if (hipMemcpy(dsrc, SrcHeightASL, sizeof(double) * n_src, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(ddist, HorizontalDistanceToRx, sizeof(double) * n, hipMemcpyHostToDevice) !=
+          hipSuccess)
+    die("hipMemcpy");
+  if (airice_table_lookup_launch_multi(&m, tables.data(), (int32_t)tables.size(), slot.data(),
+                                       RxDepthBelowIceBoundary, (int32_t)n_ant, dsrc, ddist, n_src,
+                                       IceLayerHeight, n_src, dout, n, dok, dfl, mem, work,
+                                       nullptr) != AIRICE_OK)
+    die("TableLookupBatchMulti");
+  std::vector<double> soa(9 * n);
+  std::vector<uint8_t> hok(n);
+  if (hipMemcpy(soa.data(), dout, sizeof(double) * 9 * n, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(hok.data(), dok, n, hipMemcpyDeviceToHost) != hipSuccess)
     die("hipMemcpy");
   (void)hipFree(mem);

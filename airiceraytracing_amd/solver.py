@@ -56,6 +56,49 @@ def _stream_handle(stream):
     return ctypes.c_void_p(stream.cuda_stream)  # torch.cuda.Stream
 
 
+def dedupe_depths(depths_cm):
+    """The reference's antenna -> table remap (MultiRayAirIceRefraction.cc:1348-1352): antennas at
+    exactly the same depth share the table of the first of them.  Returns (the distinct depths in
+    first-seen order, antenna_table: each antenna's index into them)."""
+    distinct: list[float] = []
+    antenna_table: list[int] = []
+    for d in (float(x) for x in depths_cm):
+        if d not in distinct:
+            distinct.append(d)
+        antenna_table.append(distinct.index(d))
+    return distinct, antenna_table
+
+
+class AntennaTables:
+    """What ``AirIceSolver.antenna_tables`` returns: the distinct antennas' packed device tables
+    (``tables``: LookupTable descriptions, ``buffers``: their 11 x n float32 tensors, ``grids``),
+    ``antenna_table`` (each antenna's index into them) and ``depths_cm``."""
+
+    def __init__(self, solver, ice_cm, grids, buffers, tables, antenna_table, depths_cm):
+        self.solver = solver
+        self.ice_cm = float(ice_cm)
+        self.grids = grids
+        self.buffers = buffers
+        self.tables = tables
+        self.antenna_table = list(antenna_table)
+        self.depths_cm = [float(d) for d in depths_cm]
+
+    def lookup(self, src_cm, dist_cm, stream=None):
+        """GetHorizontalDistanceToIntersectionPoint_Table of every (antenna, source) pair in one
+        launch: ``src_cm`` (n_src) and ``dist_cm`` (n_ant, n_src) float64 device tensors.  Returns
+        (out (9, n_ant, n_src) float64, ok (n_ant, n_src) uint8, flags (n_ant, n_src) uint8)."""
+        import torch
+        n_ant, n_src = len(self.depths_cm), int(src_cm.numel())
+        dev = src_cm.device
+        out = torch.empty((9, n_ant, n_src), dtype=torch.float64, device=dev)
+        ok = torch.empty((n_ant, n_src), dtype=torch.uint8, device=dev)
+        flags = torch.empty((n_ant, n_src), dtype=torch.uint8, device=dev)
+        self.solver.table_lookup_multi_device(self.tables, self.antenna_table, self.depths_cm,
+                                              src_cm, dist_cm, self.ice_cm, out, ok, flags,
+                                              stream=stream)
+        return out, ok, flags
+
+
 class AirIceSolver:
     """One medium (parsed GDAS atmosphere + ice model) and the batched GPU entry points."""
 
@@ -236,6 +279,61 @@ class AirIceSolver:
                                                n, ptr(out), n if ld is None else ld, ptr(ok),
                                                ptr(flags), _stream_handle(stream)),
               "airice_table_lookup_launch")
+
+    def table_lookup_multi_device(self, tables, antenna_table, antenna_depth_cm, src_cm, dist_cm,
+                                  ice_cm: float, out, ok, flags, ld: int | None = None,
+                                  work=None, stream=None):
+        """airice_table_lookup_launch_multi: the lookup of n_ant antennas x n_src sources in ONE
+        launch.  ``tables``: the distinct LookupTables (at most 32, packed or not);
+        ``antenna_table`` / ``antenna_depth_cm``: each antenna's table index and Rx depth (host);
+        ``src_cm``: n_src float64 on the device, common to all antennas (sort it once and every
+        antenna's lookups run in the faster sorted order); ``dist_cm``: an (n_ant, n_src) device
+        tensor whose row stride is passed on.  Query (a, i) lands at ``out[c, a*n_src + i]`` (9
+        columns of stride ``ld``, default n_ant*n_src), ``ok`` / ``flags`` at [a*n_src + i]: the
+        bits of one ``table_lookup_device`` call per antenna.  ``work``: a device byte tensor of
+        airice_table_lookup_multi_work_bytes, allocated here without one.  Stream-ordered; returns
+        the workspace, which must outlive the launch."""
+        import torch
+        n_tab, n_ant, n_src = len(tables), len(antenna_table), int(src_cm.numel())
+        if len(antenna_depth_cm) != n_ant:
+            raise ValueError(f"table_lookup_multi_device: {n_ant} antenna tables, "
+                             f"{len(antenna_depth_cm)} depths")
+        if n_ant > 0 and (dist_cm.dim() != 2 or tuple(dist_cm.shape) != (n_ant, n_src)
+                          or (n_src > 1 and dist_cm.stride(1) != 1)):
+            raise ValueError(f"table_lookup_multi_device: dist_cm must be ({n_ant}, {n_src}) with "
+                             f"contiguous rows, got {tuple(dist_cm.shape)}")
+        ld_dist = int(dist_cm.stride(0)) if n_ant > 1 else n_src
+        tarr = (LookupTable * max(n_tab, 1))(*tables)
+        amap = np.ascontiguousarray(antenna_table, dtype=np.int32)
+        deps = np.ascontiguousarray(antenna_depth_cm, dtype=np.float64)
+        if work is None:
+            need = int(lib().airice_table_lookup_multi_work_bytes(n_tab, n_ant))
+            work = torch.empty(max(need, 16), dtype=torch.uint8, device=src_cm.device)
+        check(lib().airice_table_lookup_launch_multi(
+            ctypes.byref(self.medium), tarr, n_tab, ptr(amap), ptr(deps), n_ant, ptr(src_cm),
+            ptr(dist_cm), ld_dist, ice_cm, n_src, ptr(out), n_ant * n_src if ld is None else ld,
+            ptr(ok), ptr(flags), ptr(work), int(work.numel()), _stream_handle(stream)),
+            "airice_table_lookup_launch_multi")
+        return work
+
+    def antenna_tables(self, depths_cm, ice_cm: float, height_step: float = 10.0,
+                       start_angle: float = 90.1, stop_angle: float = 180.0,
+                       angle_step: float = 0.1, stream=None) -> AntennaTables:
+        """The tables of a set of antennas, ready for ``AntennaTables.lookup``: antennas at the
+        same depth share one table (``dedupe_depths``, as the reference); the distinct tables are
+        made in one ``tables_device`` launch and packed."""
+        import torch
+        distinct, antenna_table = dedupe_depths(depths_cm)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        grids = [make_grid(d, ice_cm, height_step, start_angle, stop_angle, angle_step)
+                 for d in distinct]
+        buffers = [torch.empty((_lib.TABLE_COLUMNS, g.n_rays), dtype=torch.float32, device=dev)
+                   for g in grids]
+        self.tables_device(grids, buffers, stream=stream)
+        tables = [self.lookup_table(b, g) for b, g in zip(buffers, grids)]
+        for t in tables:
+            self.lookup_pack(t, stream=stream)
+        return AntennaTables(self, ice_cm, grids, buffers, tables, antenna_table, depths_cm)
 
     # ------------------------------------------------------------------ single ray (cfg1)
     def single_ray_host(self, antenna_depth: float, launch_deg: float, txh: float, ice: float,

@@ -8,7 +8,8 @@
  *
  * Where each function runs:
  *   - GPU, always: MakeRayTracingTable (.cc:2019) and the extensions MakeRayTracingTables and
- *     TableLookupBatch below -- the batch entry points (one launch chain per call).
+ *     TableLookupBatch / TableLookupBatchMulti below -- the batch entry points (one launch chain
+ *     per call).
  *   - The calling CPU thread, by default (airice_scalar_mode, include/airice.h): every one-query
  *     call -- GetRayTracingSolutions (.cc:1796), Air2IceRayTracing (.cc:1464),
  *     GetHorizontalDistanceToIntersectionPoint (.cc:945) and the ray layer (fDnfR, ftimeD,
@@ -212,6 +213,22 @@ bool TableLookup(double SrcHeightASL, double HorizontalDistanceToRx,
 void TableLookupBatch(const double* SrcHeightASL, const double* HorizontalDistanceToRx,
                       const double* RxDepthBelowIceBoundary, double IceLayerHeight, int TableIndex,
                       size_t n, double* out9, bool* ok);
+
+/* The same for n_ant antennas x n_src sources in ONE launch: query (a, i) is source height
+ * SrcHeightASL[i] (common to all antennas: sort the sources once and every antenna's lookups run
+ * in the faster sorted order), distance HorizontalDistanceToRx[a*n_src + i], depth
+ * RxDepthBelowIceBoundary[a] and antenna AntennaNumbers[a], which goes through the remap of
+ * GetHorizontalDistanceToIntersectionPoint_Table (.cc:1348-1352: the caller's AntennaDepths /
+ * AntennaTableAlreadyMade when it defines them, else the number is the table index).  out9 is
+ * (a*n_src + i) rows of the 9 outputs in the reference's argument order, ok[a*n_src + i] the
+ * returned bool: antenna a's rows are the bits of TableLookupBatch on its table.  The tables are
+ * the resident packed HBM copies TableLookupBatch uses, at most 32 distinct ones a call; each is
+ * described with the grid globals of the last table made (LoopStopHeight, HeightStepSize,
+ * TotalHeightSteps, TotalAngleSteps), exactly as TableLookupBatch does. */
+void TableLookupBatchMulti(const double* SrcHeightASL, const double* HorizontalDistanceToRx,
+                           const double* RxDepthBelowIceBoundary, double IceLayerHeight,
+                           const int* AntennaNumbers, size_t n_ant, size_t n_src, double* out9,
+                           bool* ok);
 
 }  // namespace MultiRayAirIceRefraction
 

@@ -261,6 +261,33 @@ int airice_table_lookup_launch(const airice_medium *m, const airice_lookup_table
                                double *d_out, size_t ld, uint8_t *d_ok, uint8_t *d_flags,
                                void *stream);
 
+#define AIRICE_LOOKUP_MAX_TABLES 32
+/* Batched _Table for n_ant antennas x n_src sources in ONE launch (lookup_multi_kernel).  Query
+ * (a, i): source height d_src_cm[i], distance d_dist_cm[a*ld_dist + i], Rx depth
+ * antenna_depth_cm[a], table tables[antenna_table[a]] (antennas at one depth share a table,
+ * .cc:1348-1352).  Column c of query (a, i) at d_out[c*ld + a*n_src + i]; d_ok / d_flags at
+ * [a*n_src + i].  Bit-identical (outputs, ok, flags) to one airice_table_lookup_launch per antenna.
+ * The source heights are common to all antennas, so a caller that sorts them once (and permutes
+ * the distance rows alike) gives every antenna the faster sorted order.
+ * tables (1..AIRICE_LOOKUP_MAX_TABLES of them, packed or not, each with its own grid globals),
+ * antenna_table and antenna_depth_cm (n_ant each): host arrays, read before the call returns.
+ * d_work: work_bytes >= airice_table_lookup_multi_work_bytes(n_tables, n_ant) device bytes, 16-byte
+ * aligned; the launch uploads the table descriptions and the antenna records into it.
+ * Stream-ordered, no device allocation (the upload reads the host arrays during the call, so the
+ * call is not one to capture into a graph).  An argument airice_table_lookup_launch would refuse
+ * (checked per table), n_tables outside 1..32, antenna_table[a] outside [0, n_tables),
+ * ld_dist < n_src, ld < n_ant*n_src, n_src >= 2^32 or a workspace that is too small is
+ * AIRICE_EINVAL before any device call (airice_last_error() names the offending index);
+ * n_ant == 0 or n_src == 0 is AIRICE_OK and nothing is launched. */
+size_t airice_table_lookup_multi_work_bytes(int32_t n_tables, int32_t n_ant);
+int airice_table_lookup_launch_multi(const airice_medium *m, const airice_lookup_table *tables,
+                                     int32_t n_tables, const int32_t *antenna_table,
+                                     const double *antenna_depth_cm, int32_t n_ant,
+                                     const double *d_src_cm, const double *d_dist_cm,
+                                     size_t ld_dist, double ice_cm, size_t n_src, double *d_out,
+                                     size_t ld, uint8_t *d_ok, uint8_t *d_flags, void *d_work,
+                                     size_t work_bytes, void *stream);
+
 /* --- single ray + path sampler (SingleRayAirIceRefraction, BASELINE cfg1) ---------------- */
 /* SingleRayAirIceRefraction.C:33-299 over RayTracingFunctions.cc: inputs are the CLI's values
  * after its clamps (Tx <= h_top, launch > 90, .C:40-51), metres/degrees, antenna depth
@@ -450,7 +477,8 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * of a timed kernel is bracketed by a hipEvent pair on its own stream.  Names:
  * "table_kernel", "roots_kernel" (roots_kernel / roots_sorted_kernel, the minimizer's root
  * finder), "group_passes" (the batch-wide grouping passes), "out_kernel" (solve_out /
- * hdtip_out / trace_out), "lookup_kernel", "ray_consts_kernel" and "ray_paths_kernel" (the two
+ * hdtip_out / trace_out), "lookup_kernel", "lookup_multi_kernel"
+ * (airice_table_lookup_launch_multi), "ray_consts_kernel" and "ray_paths_kernel" (the two
  * kernels of airice_ray_paths_launch).  airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -462,7 +490,8 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * "roots_kernel" (roots_kernel / roots_sorted_kernel), "scalar_solve_kernel" (the one-query
  * minimizer entry points in AIRICE_SCALAR_DEVICE mode), "out_kernel", "lookup_kernel",
  * "rtf_kernel" (ray layer and the GSL-Brent search), "single_ray_kernel", "path_kernel",
- * "ray_consts_kernel", "ray_paths_kernel" (airice_ray_paths_launch).
+ * "ray_consts_kernel", "ray_paths_kernel" (airice_ray_paths_launch), "lookup_multi_kernel"
+ * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel").
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
