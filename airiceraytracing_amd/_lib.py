@@ -148,6 +148,7 @@ LOOKUP_MAX_TABLES = 32  # AIRICE_LOOKUP_MAX_TABLES
 RTF_HIT_POINT, RTF_OPTICAL_PATH, RTF_PROPAGATION_TIME, RTF_AIR_PROPAGATION = 0, 1, 2, 3
 RTF_ICE_PROPAGATION, RTF_FDNFR, RTF_FTIMED, RTF_MIN_LAUNCH = 4, 5, 6, 7
 RTF_AIR2ICE = 8  # the Air2IceRayTracing CLI's Brent search (AIRICE_RTF_AIR2ICE_FIELDS outputs)
+RTF_AIR2ICE_FIELDS = 16  # AIRICE_RTF_AIR2ICE_FIELDS
 # MultiRayAirIceRefraction:: forms of the ray layer (AIRICE_MR_*)
 MR_FPATHD, MR_GEOMETRIC_PATH, MR_HIT_POINT, MR_AIR_PROPAGATION = 9, 10, 11, 12
 MR_ICE_PROPAGATION, MR_MIN_LAUNCH = 13, 14
@@ -162,7 +163,7 @@ EXPORTED_SYMBOLS = (
     "airice_single_ray_launch", "airice_single_ray_host", "airice_ray_paths_plan",
     "airice_ray_paths_launch", "airice_ray_paths_host", "airice_trace_ice_to_air_launch",
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
-    "airice_rtf_eval_variant", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
+    "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
     "airice_kernel_timing", "airice_kernel_time", "airice_launch_count",
     "airice_table_cache_stats", "airice_table_to_host",
@@ -239,6 +240,8 @@ def lib() -> ctypes.CDLL:
         "airice_rtf_outputs": ([I, I], I),
         "airice_rtf_eval": ([M, I, P, S, P, S], I),
         "airice_rtf_eval_variant": ([M, I, I, P, S, P, S], I),
+        "airice_air2ice_launch": ([M, P, P, P, P, S, P, S, P, P], I),
+        "airice_air2ice_host": ([M, P, P, P, P, S, P, S, P], I),
         "airice_table_to_host": ([P, S, S, P, S, P], I),
         "airice_host_register": ([P, S], I),
         "airice_host_unregister": ([P], I),

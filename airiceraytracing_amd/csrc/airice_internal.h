@@ -96,6 +96,13 @@ int launch_rtf(const DevMedium& M, int op, const double* args, size_t n_args, do
                hipStream_t st);
 int launch_trace(const DevMedium& M, const IceConsts& I, const double* depth, const double* ice,
                  const double* txh, const double* dist, size_t n, double* out10, hipStream_t st);
+// The Air2IceRayTracing.C Brent solve, batched (airice_rtf.hip): air2ice_kernel, one query per
+// lane, 16 columns of stride ld and a status byte (nullable); air2ice_host_one is the lane's
+// function on the calling thread (in: txh, dist, ice, depth).
+int launch_air2ice(const DevMedium& M, const double* txh, const double* dist, const double* ice,
+                   const double* depth, size_t n, double* out, size_t ld, uint8_t* status,
+                   hipStream_t st);
+void air2ice_host_one(const DevMedium& M, const double in[4], double* out16, uint8_t* status);
 
 static_assert(kMaxParsedLayers == kMaxLayers, "parse and kernels agree on the layer count");
 
@@ -163,6 +170,7 @@ enum KTimerId {
   KT_RAY_CONSTS,
   KT_RAY_PATHS,
   KT_LOOKUP_MULTI,
+  KT_AIR2ICE,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -190,6 +198,7 @@ enum LaunchId {
   LC_RAY_CONSTS,    // ray_consts_kernel
   LC_RAY_PATHS,     // ray_paths_kernel
   LC_LOOKUP_MULTI,  // lookup_multi_kernel
+  LC_AIR2ICE,       // air2ice_kernel (batched GSL-Brent point-to-point solve)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

@@ -407,6 +407,120 @@ __host__ __device__ void rtf_air2ice(const DevMedium& M, double AirTxHeight, dou
   o[15] = nf;
 }
 
+// ---- the same solve for a batch lane (air2ice_kernel, air2ice_host_one) ---------------------
+// The layer range of GetAirPropagationPar's loop (.cc:531-559): it depends on the two heights
+// only, so a query derives it once instead of once per launch angle.
+struct RtfLayers {
+  int top, below;  // il runs from top down to below (SkipLayersBelow)
+};
+__host__ __device__ RtfLayers rtf_layers(const DevMedium& M, double AirTxHeight,
+                                         double IceLayerHeight) {
+  RtfLayers R;
+  R.top = M.ml - rtf_skip_above(M, AirTxHeight) - 1;
+  R.below = rtf_skip_below(M, IceLayerHeight);
+  return R;
+}
+
+// What the launch-angle search reads of GetAirPropagationPar: the sum of the layers' THD and
+// L (Lvalue[0]), with no per-layer array.  Layer by layer the calls of rtf_air_prop on the same
+// arguments (the Snell step and the optical path; the receive angles and times are not read),
+// summed as rtf_min_launch and the probe loop sum them: from 0, ascending layer.  nf == 0 leaves
+// L NaN (the reference's unset slot).
+__host__ __device__ double rtf_air_thd(const DevMedium& M, const RtfLayers& R,
+                                       double LaunchAngleAir, double AirTxHeight,
+                                       double IceLayerHeight, double& Lvalue) {
+  double thd = 0, L0 = __builtin_nan("");
+  for (int il = R.top; il > R.below - 1; il--) {
+    const double StartHeight = (il == R.top) ? AirTxHeight : sel5(M.atm, il + 1) - 0.00001;
+    const double StopHeight = (il == (R.below - 1) + 1) ? IceLayerHeight : sel5(M.atm, il);
+    if (il == R.top) {
+      const double Start_nh = rtf_nz_air(M, StartHeight);
+      double ReceiveAngle;
+      rtf_hit_L(M, Start_nh, StopHeight, StartHeight, 180 - LaunchAngleAir, 1, ReceiveAngle, L0);
+    }
+    thd += rtf_optical_path(M, M.A_air, StopHeight, StartHeight, L0, 1);
+  }
+  Lvalue = L0;
+  return thd;
+}
+
+// MinimizeforLaunchAngle (.cc:683-731) over rtf_air_thd: rtf_min_launch's value, bit for bit
+__host__ __device__ double rtf_min_launch_search(const DevMedium& M, const RtfLayers& R, double x,
+                                                 double AirTxHeight, double IceLayerHeight,
+                                                 double AntennaDepth, double D) {
+  double Lvalue;
+  const double thd_air = rtf_air_thd(M, R, x, AirTxHeight, IceLayerHeight, Lvalue);
+  double thd_ice = 0;
+  if (AntennaDepth != 0) thd_ice = rtf_optical_path(M, M.A_ice, AntennaDepth, 0.0, Lvalue, 0);
+  return D - (thd_ice + thd_air);
+}
+
+// rtf_air2ice with the search on rtf_air_thd: the bracket probe and the Brent iterations read
+// the THD sum and L only; the full GetAirPropagationPar runs once, at the root.  The outputs are
+// rtf_air2ice's, bit for bit.  Every loop is bounded for every input: the probe steps 0.05 deg
+// from 90.05 until it passes endanglelim - 1 <= 179 (at most 1,779 trips; NaN limits skip it,
+// NaN < 90 is false), Brent stops at 20 iterations.
+__host__ __device__ void rtf_air2ice_search(const DevMedium& M, double AirTxHeight,
+                                            double HorizontalDistance, double IceLayerHeight,
+                                            double AntennaDepth, double* o) {
+  const RtfLayers R = rtf_layers(M, AirTxHeight, IceLayerHeight);
+  const double StraightAngle =
+      180 - (atan(HorizontalDistance / (AirTxHeight - IceLayerHeight + AntennaDepth)) * M.r2d);
+  double startanglelim = StraightAngle - 16;
+  double endanglelim = StraightAngle;
+  int probes = 0;
+  if (startanglelim < 90.00) {
+    startanglelim = 90.05;
+    bool checknan = false;
+    while (!checknan && startanglelim > 89.9) {
+      double L;
+      const double thd = rtf_air_thd(M, R, startanglelim, AirTxHeight, IceLayerHeight, L);
+      if ((!__builtin_isnan(thd) && thd > 0) || startanglelim > endanglelim - 1) {
+        checknan = true;
+      } else {
+        startanglelim = startanglelim + 0.05;
+        ++probes;
+      }
+    }
+  }
+  if (endanglelim < 90.001 && endanglelim > 90.00) endanglelim = 90.05;
+  const RtfBrent br = gsl_brent(
+      [&](double x) {
+        return rtf_min_launch_search(M, R, x, AirTxHeight, IceLayerHeight, AntennaDepth,
+                                     HorizontalDistance);
+      },
+      startanglelim, endanglelim, 0.000000001, 20);
+  const double LaunchAngleAir = br.root;
+  double air[4 * kMaxLayers + 1];
+  const int nf = rtf_air_prop(M, LaunchAngleAir, AirTxHeight, IceLayerHeight, air);
+  double thd_air = 0, t_air = 0;
+  for (int i = 0; i < nf; i++) {
+    thd_air += air[i * 4];
+    t_air += air[3 + i * 4] * 1e9;
+  }
+  const double Lvalue = nf > 0 ? air[2] : __builtin_nan("");
+  const double inc = nf > 0 ? air[1 + (nf - 1) * 4] : __builtin_nan("");
+  double ice[4];
+  rtf_ice_prop(M, AntennaDepth, Lvalue, ice);
+  const double t_ice = ice[3] * 1e9;
+  o[0] = startanglelim;
+  o[1] = endanglelim;
+  o[2] = LaunchAngleAir;
+  o[3] = thd_air;
+  o[4] = inc;
+  o[5] = Lvalue;
+  o[6] = t_air;
+  o[7] = ice[0];
+  o[8] = ice[1];
+  o[9] = t_ice;
+  o[10] = ice[0] + thd_air;
+  o[11] = t_ice + t_air;
+  o[12] = br.status | (nf == 0 ? AIRICE_SOLVE_NO_AIR_LAYER : 0);
+  o[13] = br.iters;
+  o[14] = probes;
+  o[15] = nf;
+}
+
 // ---- MultiRayAirIceRefraction:: forms (MultiRayAirIceRefraction.cc:377-917): the same
 // expressions plus the geometric path, 5-wide outputs {THD, Recv deg, L, t, geo} ----------------
 
@@ -667,7 +781,44 @@ __global__ void rtf_kernel(DevMedium M, RtfCall c, double* __restrict__ out, Sig
   signal_done(sig);
 }
 
+// The Air2IceRayTracing.C:56-185 solve of n (Tx height, distance, ice height, antenna depth)
+// queries, one per lane: the AIRICE_RTF_AIR2ICE_FIELDS values of query i at out[c*ld + i], its
+// status byte at status[i] (nullable).  Queries are independent, so a batch's results do not
+// depend on its order or size.
+constexpr int kAir2IceBlock = 256;
+__global__ __launch_bounds__(kAir2IceBlock) void air2ice_kernel(
+    DevMedium M, const double* __restrict__ txh, const double* __restrict__ dist,
+    const double* __restrict__ ice, const double* __restrict__ depth, size_t n,
+    double* __restrict__ out, size_t ld, uint8_t* __restrict__ status) {
+  const size_t i = (size_t)blockIdx.x * kAir2IceBlock + threadIdx.x;
+  if (i >= n) return;
+  double o[AIRICE_RTF_AIR2ICE_FIELDS];
+  rtf_air2ice_search(M, txh[i], dist[i], ice[i], depth[i], o);
+#pragma unroll
+  for (int c = 0; c < AIRICE_RTF_AIR2ICE_FIELDS; c++) out[(size_t)c * ld + i] = o[c];
+  if (status != nullptr) status[i] = (uint8_t)(int)o[12];
+}
+
 }  // namespace
+
+// One query of the batch solve on the calling thread: the lane's function compiled for the host.
+void air2ice_host_one(const DevMedium& M, const double in[4], double* out16, uint8_t* status) {
+  rtf_air2ice_search(M, in[0], in[1], in[2], in[3], out16);
+  if (status != nullptr) *status = (uint8_t)(int)out16[12];
+}
+
+int launch_air2ice(const DevMedium& M, const double* txh, const double* dist, const double* ice,
+                   const double* depth, size_t n, double* out, size_t ld, uint8_t* status,
+                   hipStream_t st) {
+  const size_t blocks = (n + kAir2IceBlock - 1) / kAir2IceBlock;
+  count_launch(LC_AIR2ICE);
+  ktimer_begin(KT_AIR2ICE, st);
+  hipLaunchKernelGGL(air2ice_kernel, dim3((unsigned)blocks), dim3(kAir2IceBlock), 0, st, M, txh,
+                     dist, ice, depth, n, out, ld, status);
+  const hipError_t e = hipGetLastError();
+  ktimer_end(KT_AIR2ICE, st);
+  return e == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+}
 
 // One call of any op on one lane (the kernel's lane 0 and the host form, rtf_host): r receives
 // kRtfMaxOut values, zeros past the op's outputs.

@@ -205,14 +205,15 @@ static KtPair g_kt_open[KT_COUNT];                // pair whose end is pending
 static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kernel",
                                                "group_passes",      "out_kernel",
                                                "lookup_kernel",     "ray_consts_kernel",
-                                               "ray_paths_kernel",  "lookup_multi_kernel"};
+                                               "ray_paths_kernel",  "lookup_multi_kernel",
+                                               "air2ice_kernel"};
 
 std::atomic<long long> g_launches[LC_COUNT];
 static const char* const kLcNames[LC_COUNT] = {
     "table_kernel",        "rays_kernel",  "scalar_ray_kernel", "roots_kernel",
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
-    "lookup_multi_kernel"};
+    "lookup_multi_kernel", "air2ice_kernel"};
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
 // them from a child process).
@@ -1013,6 +1014,89 @@ int airice_rtf_eval_variant(const airice_medium* m, int variant, int op, const d
   }
   if ((rc = call.sync())) return rc;
   std::memcpy(out, call.slot().h, sizeof(double) * need);
+  return AIRICE_OK;
+}
+
+// The null argument of an air2ice call, or nullptr when every required pointer is given.
+static const char* air2ice_null_arg(const void* m, const void* txh, const void* dist,
+                                    const void* ice, const void* depth, const void* out) {
+  return m == nullptr ? "m" : txh == nullptr ? "txh" : dist == nullptr ? "dist"
+       : ice == nullptr ? "ice" : depth == nullptr ? "depth" : out == nullptr ? "out" : nullptr;
+}
+
+int airice_air2ice_launch(const airice_medium* m, const double* d_txh, const double* d_dist,
+                          const double* d_ice, const double* d_depth, size_t n, double* d_out,
+                          size_t ld, uint8_t* d_status, void* stream) {
+  if (n == 0) return AIRICE_OK;
+  if (const char* a = air2ice_null_arg(m, d_txh, d_dist, d_ice, d_depth, d_out)) {
+    set_error("air2ice: null argument (%s)", a);
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("air2ice: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  if (n > (size_t)0x7fffffff * 256) {
+    set_error("air2ice: n = %zu exceeds one launch", n);
+    return AIRICE_EINVAL;
+  }
+  DevMedium M;
+  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);  // RayTracingFunctions pi (.h:26)
+  if (rc) return rc;
+  rc = airice::launch_air2ice(M, d_txh, d_dist, d_ice, d_depth, n, d_out, ld, d_status,
+                              (hipStream_t)stream);
+  if (rc) set_error("air2ice launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
+
+int airice_air2ice_host(const airice_medium* m, const double* txh, const double* dist,
+                        const double* ice, const double* depth, size_t n, double* out, size_t ld,
+                        uint8_t* status) {
+  if (n == 0) return AIRICE_OK;
+  if (const char* a = air2ice_null_arg(m, txh, dist, ice, depth, out)) {
+    set_error("air2ice: null argument (%s)", a);
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("air2ice: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  constexpr int kF = AIRICE_RTF_AIR2ICE_FIELDS;
+  if (n == 1) {  // one query: where airice_scalar_mode says
+    const double in[4] = {txh[0], dist[0], ice[0], depth[0]};
+    double o[kF];
+    uint8_t st = 0;
+    if (airice::scalar_on_host()) {
+      const DevMedium* M = nullptr;
+      if (int rc = airice::folded_medium(m, AIRICE_VARIANT_MULTIRAY, &M)) return rc;
+      airice::air2ice_host_one(*M, in, o, &st);
+    } else {
+      const int rc = airice::slot_call(
+          in, 4, 0, o, kF, &st, 1, [&](const double* d, double* q, uint8_t* f, hipStream_t s) {
+            return airice_air2ice_launch(m, d, d + 1, d + 2, d + 3, 1, q, 1, f, s);
+          });
+      if (rc) return rc;
+    }
+    for (int c = 0; c < kF; ++c) out[(size_t)c * ld] = o[c];
+    if (status) status[0] = st;
+    return AIRICE_OK;
+  }
+  // one device block: txh | dist | ice | depth | out (16 x n) | status
+  DevBuffer buf;
+  HIP_TRY(buf.alloc(sizeof(double) * (4 + kF) * n + n));
+  double* din = static_cast<double*>(buf.p);
+  double* dout = din + 4 * n;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)kF * n);
+  const double* src[4] = {txh, dist, ice, depth};
+  for (int k = 0; k < 4; ++k)
+    HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
+  const int rc = airice_air2ice_launch(m, din, din + n, din + 2 * n, din + 3 * n, n, dout, n, dst,
+                                       nullptr);
+  if (rc) return rc;
+  // the copy-back is on the null stream, like the launch: it waits for the kernel
+  HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
+                      hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
   return AIRICE_OK;
 }
 

@@ -422,17 +422,67 @@ class AirIceSolver:
                                           total), "airice_ray_paths_host")
         return summary, offsets, x, z
 
-    def paths_between(self, txh, dist, depth: float, ice: float):
+    def paths_between(self, txh, dist, depth: float, ice: float, solver: str = "multiray"):
         """The DrawShowerRays composition (DrawShowerRays.C:483-519): solve every (Tx height,
-        horizontal distance) pair against one antenna ``depth`` m below the ice surface
-        (``solve_host``, MultiRayAirIceRefraction numerics), then sample the path of every solved
-        launch angle (slot 10, LaunchAngleAir) in one batch.  Returns (summary, offsets, x, z,
-        status): ``ray_paths_host``'s outputs and the solve's AIRICE_SOLVE_* status bytes."""
+        horizontal distance) pair against one antenna ``depth`` m below the ice surface, then
+        sample the path of every solved launch angle in one batch.  ``solver="multiray"`` (the
+        default): ``solve_host``, the MultiRayAirIceRefraction bisection (slot 10, LaunchAngleAir);
+        ``solver="brent"``: ``air2ice_host``, the GSL-Brent solve of Air2IceRayTracing.C (column 2,
+        status from column 12), so the paths are the ones that program draws for each pair.
+        Returns (summary, offsets, x, z, status): ``ray_paths_host``'s outputs and the solve's
+        AIRICE_SOLVE_* status bytes."""
         h = np.ascontiguousarray(txh, dtype=np.float64).ravel()
         d = np.ascontiguousarray(np.broadcast_to(dist, h.shape), dtype=np.float64).ravel()
-        sol, status = self.solve_host(h, d, np.full(h.shape, -float(depth)), ice,
-                                      variant=VARIANT_MULTIRAY)
-        return (*self.ray_paths_host(sol[10], h, ice, float(depth)), status)
+        if solver == "brent":
+            sol, status = self.air2ice_host(h, d, float(ice), float(depth))
+            launch = sol[2]
+        elif solver == "multiray":
+            sol, status = self.solve_host(h, d, np.full(h.shape, -float(depth)), ice,
+                                          variant=VARIANT_MULTIRAY)
+            launch = sol[10]
+        else:
+            raise ValueError(f"paths_between: solver is 'multiray' or 'brent', got {solver!r}")
+        return (*self.ray_paths_host(launch, h, ice, float(depth)), status)
+
+    # ------------------------------------------------------------------ Brent solve, batched
+    def air2ice_device(self, txh, dist, ice, depth, out, status=None, ld: int | None = None,
+                       stream=None) -> None:
+        """airice_air2ice_launch: the Air2IceRayTracing.C / AirRayTracing.C point-to-point solve of
+        n pairs in one launch.  ``txh``, ``dist``, ``ice``, ``depth`` (n float64 each, m; depth
+        positive in ice, 0 for a receiver in the air at height ``ice``), ``out`` (16 x ld float64,
+        the AIRICE_RTF_AIR2ICE_FIELDS as columns) and ``status`` (n uint8, optional) are device
+        tensors.  ``out[2]`` is the contiguous launch-angle input of ``ray_paths_device``.
+        Stream-ordered."""
+        n = int(txh.numel())
+        check(lib().airice_air2ice_launch(ctypes.byref(self.medium), ptr(txh), ptr(dist), ptr(ice),
+                                          ptr(depth), n, ptr(out), n if ld is None else ld,
+                                          ptr(status), _stream_handle(stream)),
+              "airice_air2ice_launch")
+
+    def air2ice_host(self, txh, dist, ice, depth):
+        """airice_air2ice_host: numpy in, numpy out; the four inputs broadcast against each other.
+        Returns (out (16, n), status (n) uint8).  One pair runs where scalar_mode() says."""
+        arrs = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64)
+                                     for a in (txh, dist, ice, depth)])
+        t, d, i, p = [np.ascontiguousarray(a).ravel() for a in arrs]
+        n = t.size
+        out = np.empty((_lib.RTF_AIR2ICE_FIELDS, n), dtype=np.float64)
+        st = np.empty(n, dtype=np.uint8)
+        check(lib().airice_air2ice_host(ctypes.byref(self.medium), ptr(t), ptr(d), ptr(i), ptr(p),
+                                        n, ptr(out), max(n, 1), ptr(st)), "airice_air2ice_host")
+        return out, st
+
+    def air_to_air_host(self, tx_h, rx_h, dist):
+        """AirRayTracing.C for n (Tx, Rx) pairs in the air: a Tx below its Rx is swapped with it
+        (AirRayTracing.C:38-45) and the pair solved as (max, dist, min, 0) by ``air2ice_host``.
+        Returns (out (16, n), status, flipped): column 4, the incident angle on the Rx, is
+        reported as 180 - angle where ``flipped`` (AirRayTracing.C:147-157)."""
+        t, r, d = [np.ascontiguousarray(a).ravel() for a in np.broadcast_arrays(
+            *[np.asarray(a, dtype=np.float64) for a in (tx_h, rx_h, dist)])]
+        flipped = t < r
+        out, st = self.air2ice_host(np.where(flipped, r, t), d, np.where(flipped, t, r), 0.0)
+        out[4] = np.where(flipped, 180 - out[4], out[4])
+        return out, st, flipped
 
     # ------------------------------------------------------------------ pythonwrapper
     def trace_ice_to_air_device(self, depth, ice, txh, dist, out10, stream=None) -> None:

@@ -427,6 +427,31 @@ int airice_rtf_eval(const airice_medium *m, int op, const double *args, size_t n
 int airice_rtf_eval_variant(const airice_medium *m, int variant, int op, const double *args,
                             size_t n_args, double *out, size_t n_out);
 
+/* AIRICE_RTF_AIR2ICE for a batch: the point-to-point solve of the stand-alone programs
+ * Air2IceRayTracing.C:56-185 and AirRayTracing.C (launch-angle bracket and probe, GSL Brent under
+ * FindFunctionRoot, the air and ice legs at the root) for n transmitter/receiver pairs in ONE
+ * launch of air2ice_kernel, one pair per lane.  Per pair: Tx height, horizontal distance, ice
+ * height and antenna depth (m, depth > 0 in ice), so an air-to-air pair is
+ * (max(Tx, Rx), D, min(Tx, Rx), 0) (AirRayTracing.C:38-45, its receive angle reported as
+ * 180 - angle when the two were swapped) and mixes freely with air-to-ice pairs.  Value c of pair
+ * i (the AIRICE_RTF_AIR2ICE_FIELDS above) lands at d_out[c*ld + i]; d_status (nullable): value 12,
+ * the AIRICE_SOLVE_* bits, as a byte.  Column 2 (d_out + 2*ld) is a contiguous d_launch_deg for
+ * airice_ray_paths_launch.  The bits are those of airice_rtf_eval(AIRICE_RTF_AIR2ICE) on the
+ * device for each pair alone (the search reads only the summed distance and L of each trial angle,
+ * accumulated in the same order), so they do not depend on the batch or its order.  Every pair
+ * terminates, non-finite inputs included (at most 1,779 probe steps and 20 Brent iterations).
+ * Stream-ordered, no device allocation, exactly one kernel launch; n == 0 is AIRICE_OK and nothing
+ * is launched; a null required pointer or ld < n is AIRICE_EINVAL before any device call, and
+ * airice_last_error() names the argument. */
+int airice_air2ice_launch(const airice_medium *m, const double *d_txh, const double *d_dist,
+                          const double *d_ice, const double *d_depth, size_t n, double *d_out,
+                          size_t ld, uint8_t *d_status, void *stream);
+/* The same with every array on the host: n == 1 runs where airice_scalar_mode says (the calling
+ * thread, or the kernel through the one-query slot); n > 1 copies, launches and synchronises. */
+int airice_air2ice_host(const airice_medium *m, const double *txh, const double *dist,
+                        const double *ice, const double *depth, size_t n, double *out, size_t ld,
+                        uint8_t *status);
+
 /* Device bookkeeping (thin wrappers so ctypes callers need no HIP runtime binding). */
 int airice_device_count(int *count);
 int airice_set_device(int device);
@@ -479,7 +504,8 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * finder), "group_passes" (the batch-wide grouping passes), "out_kernel" (solve_out /
  * hdtip_out / trace_out), "lookup_kernel", "lookup_multi_kernel"
  * (airice_table_lookup_launch_multi), "ray_consts_kernel" and "ray_paths_kernel" (the two
- * kernels of airice_ray_paths_launch).  airice_kernel_time waits for the recorded pairs
+ * kernels of airice_ray_paths_launch), "air2ice_kernel" (airice_air2ice_launch).
+ * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
 int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, int reset);
@@ -491,7 +517,8 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * minimizer entry points in AIRICE_SCALAR_DEVICE mode), "out_kernel", "lookup_kernel",
  * "rtf_kernel" (ray layer and the GSL-Brent search), "single_ray_kernel", "path_kernel",
  * "ray_consts_kernel", "ray_paths_kernel" (airice_ray_paths_launch), "lookup_multi_kernel"
- * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel").
+ * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel"), "air2ice_kernel"
+ * (airice_air2ice_launch; it does not count as "rtf_kernel").
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
