@@ -166,7 +166,8 @@ EXPORTED_SYMBOLS = (
     "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
     "airice_kernel_timing", "airice_kernel_time", "airice_launch_count",
-    "airice_table_cache_stats", "airice_table_to_host",
+    "airice_table_cache_stats", "airice_air_cache_stats", "airice_air_cache_limits",
+    "airice_table_to_host",
     "airice_host_register", "airice_host_unregister", "airice_table_checksum",
     "airice_table_save", "airice_table_file_read_info", "airice_table_load",
 )
@@ -263,6 +264,8 @@ def lib() -> ctypes.CDLL:
         "airice_kernel_time": ([ctypes.c_char_p, ctypes.POINTER(D), ctypes.POINTER(ctypes.c_int64),
                                 I], I),
         "airice_launch_count": ([ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), I], I),
+        "airice_air_cache_stats": ([ctypes.POINTER(ctypes.c_int64)], I),
+        "airice_air_cache_limits": ([ctypes.c_int64, ctypes.c_int64], I),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -369,3 +372,18 @@ def table_cache_stats() -> dict:
     check(fn(out), "airice_table_cache_stats")
     return {"rows": {"keys": out[0], "filled": out[1], "pinned": out[2]},
             "angles": {"keys": out[3], "filled": out[4], "pinned": out[5]}}
+
+
+def air_cache_stats() -> dict:
+    """The table launch's air-record cache on the current device (airice_air_cache_stats): keys
+    seen, records filled and pinned, device bytes held, and the two byte limits."""
+    out = (ctypes.c_int64 * 6)()
+    check(lib().airice_air_cache_stats(out), "airice_air_cache_stats")
+    return dict(zip(("keys", "filled", "pinned", "bytes", "entry_limit", "total_limit"),
+                    (int(v) for v in out)))
+
+
+def air_cache_limits(entry_bytes: int = -1, total_bytes: int = -1) -> None:
+    """Byte limits of the air-record cache (airice_air_cache_limits): per record and per device;
+    a negative value keeps a limit, ``total_bytes=0`` turns the cache off."""
+    check(lib().airice_air_cache_limits(entry_bytes, total_bytes), "airice_air_cache_limits")

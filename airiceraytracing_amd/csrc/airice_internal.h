@@ -26,6 +26,10 @@ int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_gri
                        float* const* tables, const size_t* lds, hipStream_t st);
 // entries of the table launch's per-grid caches (airice_table_cache_stats)
 void table_cache_stats(int out[6]);
+// the air-record cache of the table launch (airice_air_cache_stats / airice_air_cache_limits):
+// keys, filled, pinned, bytes held on the current device, then the entry and total byte limits
+void air_cache_stats(long long out[6]);
+int air_cache_limits(long long entry_bytes, long long total_bytes);
 int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
                 int in_ice, size_t n, double* out, size_t ld, hipStream_t st);
 void rays_host(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
@@ -199,6 +203,7 @@ enum LaunchId {
   LC_RAY_PATHS,     // ray_paths_kernel
   LC_LOOKUP_MULTI,  // lookup_multi_kernel
   LC_AIR2ICE,       // air2ice_kernel (batched GSL-Brent point-to-point solve)
+  LC_AIR_PART,      // air_part_kernel (fills a table launch's air record)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

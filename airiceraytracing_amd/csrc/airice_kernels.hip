@@ -6,6 +6,10 @@
 //                         optionally, the 18 doubles of dummy[] for parity checks.
 //  table_multi_kernel   : the same block body for several antennas' tables in one grid.
 //  rowconst_kernel, angle_sines_kernel : fill the per-grid caches of the table launch.
+//  air_part_kernel      : the air part (ray_air_part) of every ray of a table launch, written to
+//                         the launch's air record; later builds of that launch, for any antenna
+//                         depth, run table_kernel's warm instantiation: record in, ice part
+//                         (ray_ice_part) only.
 //  rays_kernel          : the same ray for arbitrary (angle, height) lists.
 //  scalar_ray_kernel    : one ray (n = 1) spread over a wave.
 // Minimizer (Air2IceRayTracing, .cc:1464-1616), two stages around one shared root finder
@@ -77,6 +81,8 @@ constexpr int kLeanUnroll = 4;
 constexpr long long kMaxLaunchRays = 1LL << 30;
 // table launches of fewer rays store their columns at agent scope (table_ray's SC1)
 constexpr long long kAgentStoreRays = 1LL << 24;
+// (the warm table launch, whose air part comes from the air record, keeps that rule: cfg2 13.2 us
+// at agent scope against 16.1-16.3 us with plain stores)
 
 // ---------------------------------------------------------------------------
 // Forward ray: GetRayTracingSolutions (.cc:1796-2017).  d[] = dummy[0..17].
@@ -191,28 +197,37 @@ __host__ __device__ __forceinline__ double sel_lower_ratio(const IceConsts& I, i
   return r;
 }
 
-// want_inc: dummy[12] (the incidence angle on the ice, one asin) is not a table column
-// (.cc:2101-2111), so table launches without the double output skip it.
+// A ray is traced in two parts that meet at the ice surface.
+// The AIR PART (ray_air_part) reads the medium, the ice height's constants (I.bot, I.lower), the
+// row's constants (the Tx height) and the start sine (the launch angle) -- never the antenna depth
+// -- so its result is the same for every antenna of one grid: the table launch keeps it per ray
+// across launches (air_part_cached).  The ICE PART (ray_ice_part) forms the segment in the ice, the
+// receive angle, the Fresnel coefficients and the 18 outputs from it.  ray_solution_row is exactly
+// the air part followed by the ice part.
+struct AirPart {
+  double vinc;     // sine of the incidence on the ice; 0 when the ray crosses no air layer
+  double thd_air;  // horizontal distance, time and geometric path summed over the air layers
+  double t_air;
+  double geo_air;
+  double v;        // the running sine itself (dummy[12], want_inc)
+  bool any;        // at least one air layer
+};
+
 // top_hi >= 0: a wave-uniform upper bound of the lanes' Tx layers (the table block's first row);
 // the lower layers then run as one loop over a uniform layer index, their SegConst read with
 // scalar loads one layer at a time, instead of one inlined copy per layer.  Same operations in
 // the same order either way.
 // A1: the launch's A_air is exactly 1 (MultiRayAirIceRefraction.h:99, the table's medium), so
 // the products with it are dropped (exact: x * 1.0 == x).
+// v: sine of StartAngle (.cc:1863)
 template <bool A1 = false>
-__host__ __device__ __forceinline__ void ray_solution_row(const DevMedium& M, const IceConsts& I,
-                                                 const RowConst& rc, double theta, bool in_ice,
-                                                 double* d, bool want_inc,
-                                                 const double* tab = &kLogTable[0][0],
-                                                 int top_hi = -1,
-                                                 const double* v_start = nullptr) {
-  const double H = rc.H;
+__host__ __device__ __forceinline__ AirPart ray_air_part(const DevMedium& M, const IceConsts& I,
+                                                         const RowConst& rc, double v,
+                                                         const double* tab, int top_hi) {
   const int top = rc.top;
   const int bot = I.bot;
   const double Aair = A1 ? 1.0 : M.A_air;
   const double A2 = Aair * Aair;
-  // sine of StartAngle (.cc:1863); v_start: the same value, formed by the caller
-  double v = v_start != nullptr ? *v_start : sin_start((180 - theta) * M.d2r);
   double thd_air = 0.0, t_air = 0.0, geo_air = 0.0;
   const bool any = rc.any != 0;
   if (any) {
@@ -244,10 +259,29 @@ __host__ __device__ __forceinline__ void ray_solution_row(const DevMedium& M, co
       geo_air += s.geo;
     }
   }
-  // IncidentAngleonIce = last layer's receive angle; 0 when no air layer (.cc:1832, 1881)
-  double inc = 0.0;
-  if (want_inc) inc = any ? k_asin(v) * M.r2d : 0.0;
-  const double vinc = any ? v : 0.0;
+  AirPart a;
+  a.vinc = any ? v : 0.0;
+  // One NaN for the three sums.  An air segment's results are negated (segment_const: * -1), and
+  // the compiler may fold that negation into a neighbouring operation differently in every kernel
+  // this function is inlined into -- exact for numbers, but it leaves a NaN's sign to the kernel:
+  // the 11-column table stored -NaN as geo_air where rays_kernel's double was +NaN.  With the
+  // default NaN here the table, the air record and the per-lane rays carry the same bits.
+  a.thd_air = __builtin_isnan(thd_air) ? __builtin_nan("") : thd_air;
+  a.t_air = __builtin_isnan(t_air) ? __builtin_nan("") : t_air;
+  a.geo_air = __builtin_isnan(geo_air) ? __builtin_nan("") : geo_air;
+  a.v = v;
+  a.any = any;
+  return a;
+}
+
+// inc: dummy[12], formed by the caller (want_inc) from the air part's running sine.
+// FRESNEL = false: d[14], d[15] are left 0 (the warm table launch has them in its air record).
+template <bool FRESNEL = true>
+__host__ __device__ __forceinline__ void ray_ice_part(const DevMedium& M, const IceConsts& I,
+                                                      double H, double theta, bool in_ice,
+                                                      double vinc, double thd_air, double t_air,
+                                                      double geo_air, double inc, double* d,
+                                                      const double* tab) {
   double thd_ice = 0.0, t_ice = 0.0, geo_ice = 0.0, recv_ice = 0.0;
   if (in_ice) {
     // .cc:1897-1922: n_layer1 = Getnz_air(IceLayerHeight), Rx = -AntennaDepth, Tx = 0
@@ -260,8 +294,8 @@ __host__ __device__ __forceinline__ void ray_solution_row(const DevMedium& M, co
     geo_ice += s.geo;
     recv_ice = k_asin(v2) * M.r2d;
   }
-  double tS, tP;
-  fresnel_from_sine(I.n_air_ice, I.n_ice0, I.n_ratio, vinc, tS, tP);
+  double tS = 0.0, tP = 0.0;
+  if constexpr (FRESNEL) fresnel_from_sine(I.n_air_ice, I.n_ice0, I.n_ratio, vinc, tS, tP);
   d[0] = 0;
   d[1] = H;
   d[2] = thd_air + thd_ice;
@@ -280,6 +314,25 @@ __host__ __device__ __forceinline__ void ray_solution_row(const DevMedium& M, co
   d[15] = tP;
   d[16] = geo_air;
   d[17] = geo_ice;
+}
+
+// want_inc: dummy[12] (the incidence angle on the ice, one asin) is not a table column
+// (.cc:2101-2111), so table launches without the double output skip it.
+// v_start: the sine of StartAngle, formed by the caller.
+template <bool A1 = false>
+__host__ __device__ __forceinline__ void ray_solution_row(const DevMedium& M, const IceConsts& I,
+                                                 const RowConst& rc, double theta, bool in_ice,
+                                                 double* d, bool want_inc,
+                                                 const double* tab = &kLogTable[0][0],
+                                                 int top_hi = -1,
+                                                 const double* v_start = nullptr) {
+  // sine of StartAngle (.cc:1863); v_start: the same value, formed by the caller
+  const double v = v_start != nullptr ? *v_start : sin_start((180 - theta) * M.d2r);
+  const AirPart a = ray_air_part<A1>(M, I, rc, v, tab, top_hi);
+  // IncidentAngleonIce = last layer's receive angle; 0 when no air layer (.cc:1832, 1881)
+  double inc = 0.0;
+  if (want_inc) inc = a.any ? k_asin(a.v) * M.r2d : 0.0;
+  ray_ice_part(M, I, rc.H, theta, in_ice, a.vinc, a.thd_air, a.t_air, a.geo_air, inc, d, tab);
 }
 
 // Per-lane form (rays, minimizer evaluations): the row constants of its own Tx height.
@@ -304,7 +357,30 @@ struct TableArgs {
                               // medium and grid: row_consts_cached), or nullptr
   const double* vs;           // sin of the start angle of every column (angle_sines_cached), or
                               // nullptr
+  unsigned char* air;         // the launch's air record (air_part_cached): written by
+                              // air_part_kernel, read by the warm table_kernel; else nullptr
 };
+
+// The air record of a launch of n rays: six columns of stride n, 32 B per ray -- vinc and thd_air
+// as doubles (table column 1 is (float)(thd_air + thd_ice), so thd_air keeps its 53 bits), then
+// table columns 3 ((float)(t_air c)), 8 ((float)geo_air), 6 and 7 (the Fresnel coefficients, which
+// read vinc and the ice height's indices only) as the floats the table stores.  Keeping the two
+// Fresnel floats costs 8 B per ray of traffic and saves their ~40 FP64 operations, two square
+// roots and two quotients: cfg2 12.0 against 13.2 us.
+__host__ __device__ __forceinline__ size_t air_record_bytes(size_t n) { return 32 * n; }
+struct AirRecord {
+  double* vinc;
+  double* thd_air;
+  float* col3;
+  float* col8;
+  float* col6;
+  float* col7;
+};
+__device__ __forceinline__ AirRecord air_record(unsigned char* base, size_t n) {
+  float* f = reinterpret_cast<float*>(base + 16 * n);
+  return AirRecord{reinterpret_cast<double*>(base), reinterpret_cast<double*>(base) + n,
+                   f, f + n, f + 2 * n, f + 3 * n};
+}
 
 // Debug timeline (AIRICE_TABLE_TRACE=<file>, tools/wave_timeline.py): per wave, the 100 MHz
 // s_memrealtime at entry and exit plus HW_ID / XCC_ID.  Not part of the API.
@@ -338,6 +414,40 @@ __device__ __forceinline__ double table_angle(const TableArgs& G, int iang) {
   return th;
 }
 
+// The 11 AllTableAllAntData columns of ray k (.cc:2101-2111): the column base is wave-uniform, the
+// lane's byte offset fits 32 bits (k < 2^30 per launch).
+// (non-temporal stores: cfg2 28.9 -> 29.9 us, same bits)
+// SC1: the column stores at agent scope (global_store ... sc1), for launches short enough that
+// the lines they leave dirty in the XCDs' L2s are a visible part of the launch: cfg2 28.9-29.2
+// -> 27.8-28.2 us, the same table (without any table store the kernel takes 25.6 us); at cfg4
+// size plain stores are faster (20.8 against 21.9 ms per build)
+template <bool SC1>
+__device__ __forceinline__ void table_columns(float* __restrict__ table, size_t ld, int k, float c0,
+                                              float c1, float c2, float c3, float c4, float c5,
+                                              float c6, float c7, float c8, float c9, float c10) {
+  char* tb = reinterpret_cast<char*>(table);
+  const size_t ldb = ld * sizeof(float);
+  const uint32_t off = (uint32_t)k * 4u;
+  auto st = [&](int c, float v) {
+    float* p = reinterpret_cast<float*>(tb + c * ldb + off);
+    if constexpr (SC1)
+      st_agent(p, v);
+    else
+      *p = v;
+  };
+  st(0, c0);
+  st(1, c1);
+  st(2, c2);
+  st(3, c3);
+  st(4, c4);
+  st(5, c5);
+  st(6, c6);
+  st(7, c7);
+  st(8, c8);
+  st(9, c9);
+  st(10, c10);
+}
+
 template <bool A1, bool SC1>
 __device__ __forceinline__ void table_ray(const DevMedium& M, const IceConsts& I,
                                           const TableArgs& G, const RowConst& rc, int r, int k,
@@ -355,40 +465,57 @@ __device__ __forceinline__ void table_ray(const DevMedium& M, const IceConsts& I
     vs = sin_start((180 - th) * M.d2r);
   ray_solution_row<A1>(M, I, rc, th, G.in_ice != 0, d, full != nullptr, tab, top_hi, &vs);
   const size_t ld = G.ld;
-  // AllTableAllAntData columns (.cc:2101-2111): the column base is wave-uniform, the lane's byte
-  // offset fits 32 bits (k < 2^30 per launch)
-  {
-    char* tb = reinterpret_cast<char*>(table);
-    const size_t ldb = ld * sizeof(float);
-    const uint32_t off = (uint32_t)k * 4u;
-    // (non-temporal stores: cfg2 28.9 -> 29.9 us, same bits)
-    // SC1: the column stores at agent scope (global_store ... sc1), for launches short enough that
-    // the lines they leave dirty in the XCDs' L2s are a visible part of the launch: cfg2 28.9-29.2
-    // -> 27.8-28.2 us, the same table (without any table store the kernel takes 25.6 us); at cfg4
-    // size plain stores are faster (20.8 against 21.9 ms per build)
-    auto st = [&](int c, double v) {
-      float* p = reinterpret_cast<float*>(tb + c * ldb + off);
-      if constexpr (SC1)
-        st_agent(p, (float)v);
-      else
-        *p = (float)v;
-    };
-    st(0, d[1]);
-    st(1, d[2]);
-    st(2, d[7]);
-    st(3, d[6]);
-    st(4, d[11]);
-    st(5, d[3]);
-    st(6, d[14]);
-    st(7, d[15]);
-    st(8, d[16]);
-    st(9, d[17]);
-    st(10, d[13]);
-  }
+  table_columns<SC1>(table, ld, k, (float)d[1], (float)d[2], (float)d[7], (float)d[6],
+                     (float)d[11], (float)d[3], (float)d[14], (float)d[15], (float)d[16],
+                     (float)d[17], (float)d[13]);
   if (full != nullptr) {
 #pragma unroll
     for (int c = 0; c < 18; ++c) full[c * ld + k] = d[c];
   }
+}
+
+// The air part of table ray k alone, written to the launch's air record (air_part_kernel): the
+// expressions of table_ray and ray_solution_row up to the ice surface, then the two float columns
+// as the table stores them.
+template <bool A1>
+__device__ __forceinline__ void table_ray_air(const DevMedium& M, const IceConsts& I,
+                                              const TableArgs& G, const RowConst& rc, int r, int k,
+                                              const double* tab, int top_hi) {
+  const int iang = k - r * G.asteps;
+  double vs;
+  if (G.vs != nullptr)
+    vs = G.vs[iang];
+  else
+    vs = sin_start((180 - table_angle(G, iang)) * M.d2r);
+  const AirPart a = ray_air_part<A1>(M, I, rc, vs, tab, top_hi);
+  const AirRecord R = air_record(G.air, (size_t)G.n);
+  R.vinc[k] = a.vinc;
+  R.thd_air[k] = a.thd_air;
+  R.col3[k] = (float)(a.t_air * kSpeedC);
+  R.col8[k] = (float)a.geo_air;
+  double tS, tP;
+  fresnel_from_sine(I.n_air_ice, I.n_ice0, I.n_ratio, a.vinc, tS, tP);
+  R.col6[k] = (float)tS;
+  R.col7[k] = (float)tP;
+}
+
+// Table ray k from its air record (the warm table_kernel): the ice part on the cached vinc and
+// thd_air; columns 3, 8, 6 and 7 are the cached floats (t_air, geo_air and the Fresnel
+// coefficients enter no other column).
+template <bool SC1>
+__device__ __forceinline__ void table_ray_warm(const DevMedium& M, const IceConsts& I,
+                                               const TableArgs& G, int k,
+                                               float* __restrict__ table, const double* tab) {
+  const AirRecord R = air_record(G.air, (size_t)G.n);
+  const double vinc = R.vinc[k], thd_air = R.thd_air[k];
+  const float c3 = R.col3[k], c8 = R.col8[k], c6 = R.col6[k], c7 = R.col7[k];
+  const int r = ray_row(G, k);
+  const double th = table_angle(G, k - r * G.asteps);
+  const double H = row_height(G, G.row0 + r);  // RowConst::H of the row
+  double d[18];
+  ray_ice_part<false>(M, I, H, th, G.in_ice != 0, vinc, thd_air, 0.0, 0.0, 0.0, d, tab);
+  table_columns<SC1>(table, G.ld, k, (float)d[1], (float)d[2], (float)d[7], c3, (float)d[11],
+                     (float)d[3], c6, c7, c8, (float)d[17], (float)d[13]);
 }
 
 // Table launch: one ray per lane, ray k = block * 256 + threadIdx.x (each wave's column store one
@@ -401,7 +528,11 @@ __device__ __forceinline__ void table_ray(const DevMedium& M, const IceConsts& I
 // when capped at 64, and runs 2.7x / 7x slower -- and two rays per lane.)
 // The work of one table block (kTableBlock rays of one antenna's grid), shared by the single- and
 // the multi-antenna kernels.
-template <bool TRACE, bool A1, bool SC1>
+// MODE: kTableFull traces whole rays; kTableAir traces the air part only and writes the launch's
+// air record (no table); kTableWarm reads the air record and traces the ice part only -- it needs
+// neither the rows' constants (the Tx height comes from row_height) nor the start sines.
+enum { kTableFull = 0, kTableAir = 1, kTableWarm = 2 };
+template <bool TRACE, bool A1, bool SC1, int MODE = kTableFull>
 __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts& I,
                                             const TableArgs& G, float* __restrict__ table,
                                             double* __restrict__ full,
@@ -424,6 +555,12 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
   }
   const int k0 = (int)block * BS;
   const int ke = min(k0 + BS, G.n);  // end of this block's rays
+  if constexpr (MODE == kTableWarm) {
+    __syncthreads();
+    const int k = k0 + (int)threadIdx.x;
+    if (k < G.n) table_ray_warm<SC1>(M, I, G, k, table, &s_logtab[0][0]);
+    return;
+  }
   const int r0 = k0 < ke ? ray_row(G, k0) : 0;
   {
     const int nrows = k0 < ke ? ray_row(G, ke - 1) - r0 + 1 : 0;
@@ -433,6 +570,17 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
   }
   __syncthreads();
   const int k = k0 + (int)threadIdx.x;
+  if constexpr (MODE == kTableAir) {
+    if (k0 < G.n) {
+      const int top_hi = __builtin_amdgcn_readfirstlane(rows[0].top);
+      __builtin_assume(top_hi >= 0);
+      if (k < G.n) {
+        const int r = ray_row(G, k);
+        table_ray_air<A1>(M, I, G, rows[r - r0], r, k, &s_logtab[0][0], top_hi);
+      }
+    }
+    return;
+  }
   if (k0 < G.n) {  // block-uniform
     // the block's first row has the highest Tx, so its Tx layer bounds every lane's (top_layer is
     // monotone in the height)
@@ -452,13 +600,23 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
 }
 
 // waves_per_eu(8): 64 VGPRs at 8 waves/SIMD, measured on par or slightly ahead of 67 VGPRs at 7.
-template <bool TRACE, bool A1, bool SC1>
+// WARM: the launch has its air record (G.air, air_part_cached): the ice part only.
+template <bool TRACE, bool A1, bool SC1, bool WARM = false>
 __global__ __launch_bounds__(kTableBlock) __attribute__((amdgpu_waves_per_eu(kTableWaves, kTableWaves))) void table_kernel(
                                                    DevMedium M, IceConsts I, TableArgs G,
                                                    float* __restrict__ table,
                                                    double* __restrict__ full,
                                                    WaveTrace* __restrict__ trace) {
-  table_block<TRACE, A1, SC1>(M, I, G, table, full, trace, blockIdx.x);
+  table_block<TRACE, A1, SC1, WARM ? kTableWarm : kTableFull>(M, I, G, table, full, trace,
+                                                              blockIdx.x);
+}
+
+// Fills a launch's air record (air_part_cached): the table block's prologue and the air part of
+// every ray, one ray per lane, no table store.
+template <bool A1>
+__global__ __launch_bounds__(kTableBlock) __attribute__((amdgpu_waves_per_eu(kTableWaves, kTableWaves))) void air_part_kernel(
+    DevMedium M, IceConsts I, TableArgs G) {
+  table_block<false, A1, false, kTableAir>(M, I, G, nullptr, nullptr, nullptr, blockIdx.x);
 }
 
 // Several antennas' tables in one grid (airice_table_launch_multi): the blocks of antenna a are
@@ -2539,6 +2697,8 @@ class GridCache {
   int get(const std::vector<unsigned char>& key, size_t bytes, hipStream_t st, Fill fill,
           bool fill_first, const void** out) {
     *out = nullptr;
+    // a buffer above the byte limits is never cached: no key, no entry (set_limits)
+    if (bytes > entry_cap_ || bytes > total_cap_) return AIRICE_OK;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return AIRICE_EHIP;
     if (per_dev_.size() <= (size_t)dev) per_dev_.resize(dev + 1);
@@ -2565,6 +2725,11 @@ class GridCache {
     }
     c->used = ++D.tick;
     if (c->dev == nullptr) {  // second use: fill, stream-ordered ahead of this launch
+      // under a byte budget: free least recently used unpinned buffers first; when the pinned
+      // ones leave no room the launch goes uncached
+      bool fits = false;
+      if (int rc = trim(D, bytes, c, &fits)) return rc;
+      if (!fits) return AIRICE_OK;
       void* p = nullptr;
       if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return AIRICE_EHIP;
       fill(p, st);
@@ -2577,6 +2742,7 @@ class GridCache {
         return AIRICE_EHIP;
       }
       c->dev = p;
+      c->bytes = bytes;
       c->ev = ev;
       c->origin = st;
       *out = p;
@@ -2597,16 +2763,39 @@ class GridCache {
   }
 
   // entries of the current device (tests: airice_table_cache_stats)
-  void stats(int* keys, int* filled, int* pinned) {
+  void stats(int* keys, int* filled, int* pinned, size_t* bytes = nullptr) {
     int dev = 0;
     *keys = *filled = *pinned = 0;
+    if (bytes != nullptr) *bytes = 0;
     if (hipGetDevice(&dev) != hipSuccess || per_dev_.size() <= (size_t)dev) return;
     for (const Entry& e : per_dev_[dev].entries) {
       ++*keys;
       *filled += e.dev != nullptr;
       *pinned += e.pinned;
+      if (bytes != nullptr) *bytes += e.bytes;
     }
   }
+
+  // Byte limits (the air record's cache; the row and sine caches have none): a buffer larger than
+  // entry_cap is never cached, and the buffers of one device hold at most total_cap bytes --
+  // least recently used unpinned buffers are freed to make room, their keys stay.  Lowering the
+  // total frees down to it at once, on every device; a total of 0 (the cache switched off) also
+  // forgets the keys of all unpinned entries.
+  int set_limits(size_t entry_cap, size_t total_cap) {
+    entry_cap_ = entry_cap;
+    total_cap_ = total_cap;
+    for (Dev& D : per_dev_) {
+      bool fits = false;
+      if (int rc = trim(D, 0, nullptr, &fits)) return rc;
+      if (total_cap == 0)
+        D.entries.erase(std::remove_if(D.entries.begin(), D.entries.end(),
+                                       [](const Entry& e) { return !e.pinned; }),
+                        D.entries.end());
+    }
+    return AIRICE_OK;
+  }
+  size_t entry_cap() const { return entry_cap_; }
+  size_t total_cap() const { return total_cap_; }
 
  private:
   struct Entry {
@@ -2617,6 +2806,7 @@ class GridCache {
     bool ready = false;         // the fill is known complete
     bool pinned = false;        // handed to a captured launch: never evicted
     unsigned long long used = 0;
+    size_t bytes = 0;           // of the buffer
   };
   struct Dev {
     std::vector<Entry> entries;
@@ -2637,7 +2827,31 @@ class GridCache {
     D.entries.erase(D.entries.begin() + (long)old);
     return AIRICE_OK;
   }
+  // Frees least recently used unpinned buffers of D (not keep's) until `need` more bytes fit
+  // under total_cap_; an entry whose buffer is freed is back to "seen once".  hipFree waits for
+  // the kernels still reading the buffer.
+  int trim(Dev& D, size_t need, const Entry* keep, bool* fits) {
+    for (;;) {
+      size_t held = 0;
+      Entry* old = nullptr;
+      for (Entry& e : D.entries) {
+        held += e.bytes;
+        if (e.dev == nullptr || e.pinned || &e == keep) continue;
+        if (old == nullptr || e.used < old->used) old = &e;
+      }
+      *fits = need <= total_cap_ && held <= total_cap_ - need;
+      if (*fits || total_cap_ == SIZE_MAX || old == nullptr) return AIRICE_OK;
+      if (hipFree(old->dev) != hipSuccess) return AIRICE_EHIP;
+      if (old->ev != nullptr) (void)hipEventDestroy(old->ev);
+      old->dev = nullptr;
+      old->ev = nullptr;
+      old->origin = nullptr;
+      old->ready = false;
+      old->bytes = 0;
+    }
+  }
   std::vector<Dev> per_dev_;
+  size_t entry_cap_ = SIZE_MAX, total_cap_ = SIZE_MAX;
 };
 
 static GridCache& row_cache() {
@@ -2700,6 +2914,106 @@ static int angle_sines_cached(const DevMedium& M, const TableArgs& A, hipStream_
   return rc;
 }
 
+// The air part of every ray of one launch (AirRecord; air_part_kernel), kept across launches: it
+// reads the medium, the ice height's air-side constants, the row's Tx height and the column's
+// launch angle, but not the antenna, so from the second table of one grid on -- one table per
+// antenna depth, RunMultiRayCode.C:29-52 -- a build traces the ice segment only (the warm
+// table_kernel).  Same entry life cycle as the two caches above, never filled at first use.  The
+// key is the bytes of everything ray_air_part, row_const and the Fresnel coefficients read -- the
+// medium, I.bot, I.lower, I.topend, the two indices at the ice surface and their ratio, the height
+// grid, the angle grid -- and the launch's row range, so a row slab keeps its own rays; the
+// antenna depth (I.iceseg, I.ice_rx) and in_ice are not in it.
+// A record is 32 B per ray, so this cache has byte limits instead of an entry count alone: no
+// record above kAirEntryBytes (cfg4-sized launches are never cached), kAirTotalBytes per device.
+// AIRICE_AIR_CACHE_MB=<n> sets the per-device total (and caps the entry limit at it), 0 turns the
+// cache off; airice_air_cache_limits sets both in-process.
+constexpr size_t kAirEntryBytes = (size_t)320 << 20;  // the reference's default grid: 8.73e6 rays, 279 MB
+constexpr size_t kAirTotalBytes = (size_t)640 << 20;
+static GridCache& air_cache() {
+  static GridCache c = [] {
+    GridCache g;
+    size_t entry = kAirEntryBytes, total = kAirTotalBytes;
+    if (const char* e = getenv("AIRICE_AIR_CACHE_MB")) {
+      char* end = nullptr;
+      const long long mb = strtoll(e, &end, 10);
+      if (end != e && mb >= 0) {
+        total = (size_t)mb << 20;
+        entry = std::min(entry, total);
+      }
+    }
+    (void)g.set_limits(entry, total);
+    return g;
+  }();
+  return c;
+}
+
+template <bool A1>
+static void launch_air_part(const DevMedium& M, const IceConsts& I, const TableArgs& A,
+                            hipStream_t s) {
+  const unsigned blocks = (unsigned)((A.n + kTableBlock - 1) / kTableBlock);
+  hipLaunchKernelGGL(air_part_kernel<A1>, dim3(blocks), dim3(kTableBlock),
+                     sizeof(RowConst) * (size_t)A.rows_per_block, s, M, I, A);
+}
+
+// A: the launch's arguments with row0, n and the row / sine caches set.  rows: its row count.
+static int air_part_cached(const DevMedium& M, const IceConsts& I, const TableArgs& A, int rows,
+                           hipStream_t st, unsigned char** out) {
+  *out = nullptr;
+  const size_t bytes = air_record_bytes((size_t)A.n);
+  if (bytes == 0 || bytes > air_cache().entry_cap() || bytes > air_cache().total_cap())
+    return AIRICE_OK;  // before the key is built: a launch that is never cached pays nothing
+  const double gk[6] = {A.start_h, A.stop_h, A.step_h, A.start_a, A.stop_a, A.step_a};
+  const int ik[4] = {A.hsteps, A.asteps, A.row0, rows};
+  const double fk[3] = {I.n_air_ice, I.n_ice0, I.n_ratio};
+  std::vector<unsigned char> key(sizeof(M) + sizeof(I.bot) + sizeof(I.lower) + sizeof(I.topend) +
+                                 sizeof(fk) + sizeof(gk) + sizeof(ik));
+  unsigned char* kp = key.data();
+  auto put = [&kp](const void* p, size_t n) {
+    std::memcpy(kp, p, n);
+    kp += n;
+  };
+  put(&M, sizeof(M));
+  put(&I.bot, sizeof(I.bot));
+  put(I.lower, sizeof(I.lower));
+  put(I.topend, sizeof(I.topend));
+  put(fk, sizeof(fk));
+  put(gk, sizeof(gk));
+  put(ik, sizeof(ik));
+  auto fill = [&](void* p, hipStream_t s) {
+    TableArgs F = A;
+    F.air = static_cast<unsigned char*>(p);
+    count_launch(LC_AIR_PART);
+    if (M.A_air == 1.0)
+      launch_air_part<true>(M, I, F, s);
+    else
+      launch_air_part<false>(M, I, F, s);
+  };
+  const void* p = nullptr;
+  const int rc = air_cache().get(key, bytes, st, fill, false, &p);
+  *out = static_cast<unsigned char*>(const_cast<void*>(p));
+  return rc;
+}
+
+void air_cache_stats(long long out[6]) {
+  std::lock_guard<std::mutex> lock(grid_cache_mutex());
+  int k = 0, f = 0, p = 0;
+  size_t b = 0;
+  air_cache().stats(&k, &f, &p, &b);
+  auto lim = [](size_t v) { return v > (size_t)INT64_MAX ? (long long)INT64_MAX : (long long)v; };
+  out[0] = k;
+  out[1] = f;
+  out[2] = p;
+  out[3] = (long long)b;
+  out[4] = lim(air_cache().entry_cap());
+  out[5] = lim(air_cache().total_cap());
+}
+
+int air_cache_limits(long long entry_bytes, long long total_bytes) {
+  std::lock_guard<std::mutex> lock(grid_cache_mutex());
+  GridCache& c = air_cache();
+  return c.set_limits(entry_bytes < 0 ? c.entry_cap() : (size_t)entry_bytes,
+                      total_bytes < 0 ? c.total_cap() : (size_t)total_bytes);
+}
 
 void table_cache_stats(int out[6]) {
   std::lock_guard<std::mutex> lock(grid_cache_mutex());
@@ -2743,6 +3057,13 @@ int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, i
   static const char* trace_path = getenv("AIRICE_TABLE_TRACE");
   // ray indices are 32-bit inside a launch: grids of kMaxLaunchRays or more go in row slabs
   const int max_rows = (int)std::max<long long>(1, (kMaxLaunchRays - 2 * kTableBlock) / g->angle_steps);
+  // a plain build (11 columns, one launch) of a launch seen before reads its rays' air part from
+  // the air record and traces the ice segment only
+  if (d_full == nullptr && trace_path == nullptr && row_count <= max_rows) {
+    A.row0 = row_begin;
+    A.n = row_count * g->angle_steps;
+    if (int rc = air_part_cached(M, I, A, row_count, st, &A.air)) return rc;
+  }
   for (int done = 0; done < row_count;) {
     const int rows = std::min(max_rows, row_count - done);
     const size_t off = (size_t)done * (size_t)g->angle_steps;
@@ -2761,8 +3082,10 @@ int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, i
       auto kern = M.A_air == 1.0
                       ? (sc1 ? table_kernel<false, true, true> : table_kernel<false, true, false>)
                       : (sc1 ? table_kernel<false, false, true> : table_kernel<false, false, false>);
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(kTableBlock), lds, st, M, I, A, tab, full,
-                         nullptr);
+      if (A.air != nullptr)
+        kern = sc1 ? table_kernel<false, false, true, true> : table_kernel<false, false, false, true>;
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(kTableBlock), A.air != nullptr ? 0 : lds, st, M,
+                         I, A, tab, full, nullptr);
       ktimer_end(KT_TABLE, st);
       if (hipGetLastError() != hipSuccess) return AIRICE_EHIP;
       continue;

@@ -213,7 +213,8 @@ static const char* const kLcNames[LC_COUNT] = {
     "table_kernel",        "rays_kernel",  "scalar_ray_kernel", "roots_kernel",
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
-    "lookup_multi_kernel", "air2ice_kernel"};
+    "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel"};
+static_assert(sizeof(kLcNames) / sizeof(kLcNames[0]) == LC_COUNT, "one name per counter");
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
 // them from a child process).
@@ -475,6 +476,23 @@ extern "C" int airice_table_cache_stats(int out[6]) {
   }
   table_cache_stats(out);
   return AIRICE_OK;
+}
+
+extern "C" int airice_air_cache_stats(int64_t out[6]) {
+  if (out == nullptr) {
+    set_error("airice_air_cache_stats: out is null");
+    return AIRICE_EINVAL;
+  }
+  long long v[6];
+  air_cache_stats(v);
+  for (int i = 0; i < 6; ++i) out[i] = (int64_t)v[i];
+  return AIRICE_OK;
+}
+
+extern "C" int airice_air_cache_limits(int64_t entry_bytes, int64_t total_bytes) {
+  const int rc = air_cache_limits((long long)entry_bytes, (long long)total_bytes);
+  if (rc != AIRICE_OK) set_error("airice_air_cache_limits: freeing a cached air record failed");
+  return rc;
 }
 
 extern "C" int airice_kernel_timing(int on) {

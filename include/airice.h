@@ -518,7 +518,8 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * "rtf_kernel" (ray layer and the GSL-Brent search), "single_ray_kernel", "path_kernel",
  * "ray_consts_kernel", "ray_paths_kernel" (airice_ray_paths_launch), "lookup_multi_kernel"
  * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel"), "air2ice_kernel"
- * (airice_air2ice_launch; it does not count as "rtf_kernel").
+ * (airice_air2ice_launch; it does not count as "rtf_kernel"), "air_part_kernel" (the fill of a
+ * table launch's air record, below; it does not count as "table_kernel").
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
@@ -529,6 +530,24 @@ int airice_launch_count(const char *name, int64_t *count, int reset);
  * sines.  A grid's first launch only records its key; the second fills the buffers, stream-ordered
  * (INTEGRATION.md §5). */
 int airice_table_cache_stats(int out[6]);
+
+/* The table launch's air record (no reference counterpart).  The path of a table ray through the
+ * air depends on the medium, the ice height, the Tx height and the launch angle, not on the
+ * antenna: airice_table_launch keeps it per ray (32 bytes) for a launch -- medium, ice height,
+ * grid and row range -- it has seen before, and later 11-column builds of that launch, for any
+ * antenna depth, trace the ice segment only.  First use of a launch records its key, the second
+ * fills the record (air_part_kernel, stream-ordered), later ones read it; tables are bit for bit
+ * the uncached ones.  Launches with the 18-double output and airice_table_launch_multi do not use
+ * it.
+ * airice_air_cache_stats: out[0..3] = keys seen, records filled, records pinned by a captured
+ * launch, bytes of device memory held, on the current device; out[4..5] = the limits below.
+ * airice_air_cache_limits: a record above entry_bytes is never cached, the records of one device
+ * hold at most total_bytes (least recently used unpinned records are freed first); a negative
+ * value keeps a limit, total_bytes = 0 turns the cache off and drops every unpinned record
+ * and key.  Defaults: 320 MiB and 640 MiB;
+ * AIRICE_AIR_CACHE_MB=<n> in the environment sets the total (0: off). */
+int airice_air_cache_stats(int64_t out[6]);
+int airice_air_cache_limits(int64_t entry_bytes, int64_t total_bytes);
 
 #ifdef __cplusplus
 }
