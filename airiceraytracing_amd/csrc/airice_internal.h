@@ -1,4 +1,10 @@
 // airice_internal.h -- host-side internals shared by the runtime and the launchers.
+//
+// The kernels live in airice_table.hip (forward ray: table, rays), airice_solve.hip (minimizer),
+// airice_lookup.hip (the lookup's pack kernels), airice_path.hip and airice_rtf.hip; each opens
+// with its own inventory.
+// Data layout in HBM: structure-of-arrays, column c of item i at out[c*ld + i], so each
+// wave's store of one column is one contiguous 256 B (f32) / 512 B (f64) segment.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,7 +15,19 @@
 #include "airice_device.hpp"
 #include "airice_host.h"
 
+// Library-internal names that are new to a header: kept out of libairice.so's dynamic symbols.
+#define AIRICE_LOCAL __attribute__((visibility("hidden")))
+
 namespace airice {
+
+// Launch-shape constants and launcher helpers shared by the kernel units.
+constexpr int kBlock = 256;
+constexpr int kRootsWaves = 4;  // 127 VGPRs: 4 waves/SIMD (5 and 6 spill and run slower)
+inline unsigned grid_for(long long n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+inline int launch_ok() { return hipGetLastError() == hipSuccess ? AIRICE_OK : AIRICE_EHIP; }
+// AIRICE_BISECT_EXACT=1 (debug / validation): the root finder evaluates every bisection midpoint
+// (airice_solve.hip).
+AIRICE_LOCAL int bisect_exact();
 
 // Kernel-argument medium for one variant (pi) built from the parsed medium; the
 // layer-boundary endpoints are evaluated here, on the host, once.
@@ -34,7 +52,7 @@ int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, co
                 int in_ice, size_t n, double* out, size_t ld, hipStream_t st);
 void rays_host(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
                int in_ice, size_t n, double* out, size_t ld);
-// one query of the minimizer entry points on the host (airice_kernels.hip: solve_one_host_t)
+// one query of the minimizer entry points on the host (airice_solve.hip: solve_one_host_t)
 int solve_host_one(const DevMedium& M, const IceConsts& I, int variant, const double* in,
                    bool has_thr, double* out, uint8_t* status);
 int hdtip_host_one(const DevMedium& M, const IceConsts& I, double ice_cm, const double* in,
@@ -54,7 +72,7 @@ hipError_t scratch_alloc(void** p, size_t bytes, hipStream_t st);
 // (AIRICE_GROUP_MIN overrides it; 0 when a source never groups by default).
 size_t group_min_batch(int in);
 // Table lookup: lookup_kernel, each AIRICE_LOOKUP_FALLBACK lane solving its minimizer fallback
-// in place (airice_kernels.hip; the pack kernels: airice_lookup.hip).
+// in place (airice_solve.hip; the pack kernels: airice_lookup.hip).
 int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_table* t,
                   const double* src, const double* dist, const double* depth, double ice_cm,
                   size_t n, double* out, size_t ld, uint8_t* ok, uint8_t* flags, hipStream_t st);

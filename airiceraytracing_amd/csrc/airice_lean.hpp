@@ -1,7 +1,7 @@
 // airice_lean.hpp -- the guarded bisection's evaluation-free steps in closed form (device, and
 // compiled by g++ for tests/cpp/lean_check.cpp, which checks it against the step-by-step form).
 //
-// solve_root (airice_kernels.hip) replays GSL's bisection (gsl_root_fsolver_bisection +
+// solve_root (airice_minimizer.hpp) replays GSL's bisection (gsl_root_fsolver_bisection +
 // gsl_root_test_interval(lo, hi, 0, 1e-9) + max_iter 40, MultiRayAirIceRefraction.cc:340-374).
 // Between two evaluations it runs the steps whose midpoint lies in a guard region -- xm <= gl
 // (f has f(lo)'s sign there: lo moves) or xm >= gr (hi moves) -- until a midpoint falls strictly

@@ -13,8 +13,12 @@
 //                  A lane that hits the one-sided extrapolation case (.cc:1418) is flagged
 //                  (AIRICE_LOOKUP_FALLBACK) and runs the reference's minimizer fallback in place:
 //                  the root finder, then stage 2 of the fallback entry point with the root in
-//                  registers (EntryPoint<OUT_FALLBACK>, airice_kernels.hip, where the kernel
-//                  lives).  A one-query call solves its fallback through launch_lookup_fallback.
+//                  registers (EntryPoint<OUT_FALLBACK>, airice_minimizer.hpp).  The kernel, its
+//                  multi-antenna form lookup_multi_kernel and their launchers live in
+//                  airice_solve.hip, the unit that holds the root finder's other instantiations;
+//                  this unit has the kernels that build the packed copy of a table
+//                  (launch_lookup_pack).  A one-query call solves its fallback through
+//                  launch_lookup_fallback.
 //
 // Cost model: every lane gathers its own lines, so the kernel is bound by the 128-byte lines it
 // pulls from L2 / the Infinity Cache per query, not by bytes.  With the packed copy a query reads

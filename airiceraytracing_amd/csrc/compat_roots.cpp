@@ -9,7 +9,7 @@
 // roots/bisection.c (the Air2Ice minimizer, .cc:1521) and roots/brent.c (the RTF CLIs,
 // Air2IceRayTracing.C:137), with roots/fsolver.c's set and roots/convergence.c's interval test.
 // The search calls a host function pointer, so it runs on the host; the GPU kernels carry their
-// own device forms of the same two machines (airice_kernels.hip, airice_rtf.hip).
+// own device forms of the same two machines (airice_minimizer.hpp, airice_rtf.hip).
 //
 // Undefined reference behaviour is modelled as the device and the test oracle model it: when
 // f(x_lo) or f(x_hi) is not finite, GSL's set returns before storing its state and iterate then

@@ -1,4 +1,4 @@
-"""CPU simulation of the minimizer's root search (solve_root, airice_kernels.hip) to count
+"""CPU simulation of the minimizer's root search (solve_root, airice_minimizer.hpp) to count
 f-evaluations per solve for alternative search / guard strategies (tools only; the GPU's own counts
 come from tools/solve_stats.py).  f(theta) = D - THD(theta) is taken from the oracle's forward ray
 (GetRayTracingSolutions), a close stand-in for MinimizeforLaunchAngle's f; unprobed cfg3 queries.

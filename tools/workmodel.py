@@ -1,7 +1,7 @@
 """Algorithmic FP64 work per table ray.
 
 W_ray = sum_f n_f * w_f + n_arith, where n_f counts the UNIQUE transcendental / divide
-evaluations a table ray needs for its 11 output columns (airice_kernels.hip ray_solution_row,
+evaluations a table ray needs for its 11 output columns (airice_ray.hpp ray_solution_row,
 airice_device.hpp segment_const), w_f is the gfx950 ocml FP64 instruction cost of f
 (tools/opweights.json, measured with rocprofv3 --pmc) and n_arith the add/mul/fma count.
 Work that depends on the Tx height only (row constants) is amortised over the row's angles;
