@@ -152,6 +152,24 @@ RTF_AIR2ICE_FIELDS = 16  # AIRICE_RTF_AIR2ICE_FIELDS
 # MultiRayAirIceRefraction:: forms of the ray layer (AIRICE_MR_*)
 MR_FPATHD, MR_GEOMETRIC_PATH, MR_HIT_POINT, MR_AIR_PROPAGATION = 9, 10, 11, 12
 MR_ICE_PROPAGATION, MR_MIN_LAUNCH = 13, 14
+# airice_iceray_launch / _host (IceRayTracing::IceRayTracing): columns and status bits.  A column
+# base + k is ray k of (direct, reflected, refracted 0, refracted 1) where the base has four.
+ICERAY_FIELDS = 32             # AIRICE_ICERAY_FIELDS: the reference's 29, then three diagnostics
+ICERAY_REFERENCE_FIELDS = 29   # IceRayTracing's output[0..28]
+ICERAY_LAUNCH_ANGLE = 0        # 0-3, deg
+ICERAY_TIME = 4                # 4-7, s
+ICERAY_RECEIVE_ANGLE = 8       # 8-11, deg; -1000 when the ray does not exist
+ICERAY_LEG_TIMES = 12          # 12-13 R, 14-15 Ra0, 16-17 Ra1: Tx to top, top to Rx (0.0: no ray)
+ICERAY_INCIDENCE = 18          # the reflected ray's angle of incidence at the surface, deg
+ICERAY_LVALUE = 19             # 19-22
+ICERAY_ZMAX = 23               # 23-24: turning depths of the refracted rays, m
+ICERAY_PATH = 25               # 25-28, m
+ICERAY_STATUS = 29             # the status byte as a double
+ICERAY_EVALS = 30              # residual evaluations
+ICERAY_ITERS = 31              # false-position iterations of the direct search
+ICERAY_D, ICERAY_R, ICERAY_RA0, ICERAY_RA1 = 1, 2, 4, 8  # status: ray accepted
+ICERAY_NONFINITE = 128         # status: NaN or infinite input, no search
+ICERAY_DEFAULT_MODEL = (1.78, -0.43, 0.0132)  # A, B, C of n(z) = A + B exp(-C|z|)
 
 EXPORTED_SYMBOLS = (
     "airice_last_error", "airice_version", "airice_atmosphere_load", "airice_atmosphere_parse",
@@ -163,7 +181,8 @@ EXPORTED_SYMBOLS = (
     "airice_single_ray_launch", "airice_single_ray_host", "airice_ray_paths_plan",
     "airice_ray_paths_launch", "airice_ray_paths_host", "airice_trace_ice_to_air_launch",
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
-    "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
+    "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host",
+    "airice_iceray_launch", "airice_iceray_host", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
     "airice_kernel_timing", "airice_kernel_time", "airice_launch_count",
     "airice_table_cache_stats", "airice_air_cache_stats", "airice_air_cache_limits",
@@ -243,6 +262,8 @@ def lib() -> ctypes.CDLL:
         "airice_rtf_eval_variant": ([M, I, I, P, S, P, S], I),
         "airice_air2ice_launch": ([M, P, P, P, P, S, P, S, P, P], I),
         "airice_air2ice_host": ([M, P, P, P, P, S, P, S, P], I),
+        "airice_iceray_launch": ([P, P, P, P, S, P, S, P, P], I),
+        "airice_iceray_host": ([P, P, P, P, S, P, S, P], I),
         "airice_table_to_host": ([P, S, S, P, S, P], I),
         "airice_host_register": ([P, S], I),
         "airice_host_unregister": ([P], I),

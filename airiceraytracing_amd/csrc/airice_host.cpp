@@ -12,6 +12,7 @@
 
 #include "airice.h"
 #include "airice_host.h"
+#include "airice_iceray.hpp"
 
 namespace airice {
 
@@ -255,6 +256,13 @@ struct FileCloser {
 };
 
 }  // namespace
+
+// The in-ice solver's host route: the lane function of iceray_kernel on the calling thread.
+void iceray_host_one(const double model[3], const double in[3], double* out32, uint8_t* status) {
+  const iceray::IceModel m = {model[0], model[1], model[2]};
+  const uint8_t st = iceray::solve_pair(m, in[0], in[1], in[2], iceray::ArrayOut{out32});
+  if (status != nullptr) *status = st;
+}
 
 }  // namespace airice
 

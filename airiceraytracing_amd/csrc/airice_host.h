@@ -17,5 +17,8 @@ double variant_pi(int variant);
 // readATMpar + readnhFromFile + spline + FillInAirRefractiveIndex (.cc:24-213, 920-942) on a
 // text image of a GDAS Atmosphere.dat, with the reference's stream semantics
 int parse_gdas(const std::string& text, airice_medium* m);
+// One (z0, x1, z1) pair of the in-ice solver on the calling thread (airice_iceray.hpp compiled
+// for the host): model = {A, B, C}, out32 = the AIRICE_ICERAY_FIELDS values, status nullable.
+void iceray_host_one(const double model[3], const double in[3], double* out32, uint8_t* status);
 
 }  // namespace airice

@@ -125,6 +125,11 @@ int launch_air2ice(const DevMedium& M, const double* txh, const double* dist, co
                    const double* depth, size_t n, double* out, size_t ld, uint8_t* status,
                    hipStream_t st);
 void air2ice_host_one(const DevMedium& M, const double in[4], double* out16, uint8_t* status);
+// The in-ice solver, batched (airice_iceray.hip): iceray_kernel, one (z0, x1, z1) pair per lane,
+// AIRICE_ICERAY_FIELDS columns of stride ld and a status byte (nullable); model = {A, B, C}.  The
+// lane's function on the calling thread is iceray_host_one (airice_host.h).
+int launch_iceray(const double model[3], const double* z0, const double* x1, const double* z1,
+                  size_t n, double* out, size_t ld, uint8_t* status, hipStream_t st);
 
 static_assert(kMaxParsedLayers == kMaxLayers, "parse and kernels agree on the layer count");
 
@@ -193,6 +198,7 @@ enum KTimerId {
   KT_RAY_PATHS,
   KT_LOOKUP_MULTI,
   KT_AIR2ICE,
+  KT_ICERAY,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -222,6 +228,7 @@ enum LaunchId {
   LC_LOOKUP_MULTI,  // lookup_multi_kernel
   LC_AIR2ICE,       // air2ice_kernel (batched GSL-Brent point-to-point solve)
   LC_AIR_PART,      // air_part_kernel (fills a table launch's air record)
+  LC_ICERAY,        // iceray_kernel (batched in-ice direct / reflected / refracted solve)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

@@ -206,14 +206,14 @@ static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kerne
                                                "group_passes",      "out_kernel",
                                                "lookup_kernel",     "ray_consts_kernel",
                                                "ray_paths_kernel",  "lookup_multi_kernel",
-                                               "air2ice_kernel"};
+                                               "air2ice_kernel",    "iceray_kernel"};
 
 std::atomic<long long> g_launches[LC_COUNT];
 static const char* const kLcNames[LC_COUNT] = {
     "table_kernel",        "rays_kernel",  "scalar_ray_kernel", "roots_kernel",
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
-    "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel"};
+    "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel", "iceray_kernel"};
 static_assert(sizeof(kLcNames) / sizeof(kLcNames[0]) == LC_COUNT, "one name per counter");
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
@@ -1095,6 +1095,93 @@ int airice_air2ice_host(const airice_medium* m, const double* txh, const double*
     HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
   const int rc = airice_air2ice_launch(m, din, din + n, din + 2 * n, din + 3 * n, n, dout, n, dst,
                                        nullptr);
+  if (rc) return rc;
+  // the copy-back is on the null stream, like the launch: it waits for the kernel
+  HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
+                      hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
+  return AIRICE_OK;
+}
+
+// ---- the in-ice solver (IceRayTracing::IceRayTracing), batched ---------------------------------
+static const double kIceRayDefaultModel[3] = {1.78, -0.43, 0.0132};  // IceRayTracing.hh:52-54
+
+// The null argument of an iceray call, or nullptr when every required pointer is given.
+static const char* iceray_null_arg(const void* z0, const void* x1, const void* z1,
+                                   const void* out) {
+  return z0 == nullptr ? "z0" : x1 == nullptr ? "x1" : z1 == nullptr ? "z1"
+       : out == nullptr ? "out" : nullptr;
+}
+
+int airice_iceray_launch(const double* model3, const double* d_z0, const double* d_x1,
+                         const double* d_z1, size_t n, double* d_out, size_t ld,
+                         uint8_t* d_status, void* stream) {
+  if (n == 0) return AIRICE_OK;
+  if (const char* a = iceray_null_arg(d_z0, d_x1, d_z1, d_out)) {
+    set_error("iceray: null argument (%s)", a);
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("iceray: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  if (n > (size_t)0x7fffffff * 256) {
+    set_error("iceray: n = %zu exceeds one launch", n);
+    return AIRICE_EINVAL;
+  }
+  const int rc = airice::launch_iceray(model3 != nullptr ? model3 : kIceRayDefaultModel, d_z0,
+                                       d_x1, d_z1, n, d_out, ld, d_status, (hipStream_t)stream);
+  if (rc) set_error("iceray launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
+
+int airice_iceray_host(const double* model3, const double* z0, const double* x1, const double* z1,
+                       size_t n, double* out, size_t ld, uint8_t* status) {
+  if (n == 0) return AIRICE_OK;
+  if (const char* a = iceray_null_arg(z0, x1, z1, out)) {
+    set_error("iceray: null argument (%s)", a);
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("iceray: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  constexpr int kF = AIRICE_ICERAY_FIELDS;
+  if (n == 1) {  // one pair: where airice_scalar_mode says
+    const double in[3] = {z0[0], x1[0], z1[0]};
+    double o[kF];
+    uint8_t st = 0;
+    if (airice::scalar_on_host()) {
+      airice::iceray_host_one(model3 != nullptr ? model3 : kIceRayDefaultModel, in, o, &st);
+    } else {
+      // the scalar slot: inputs at h[0..2], the 32 outputs from h[8], the status byte at h + 48
+      constexpr int kOut = 8, kFlag = 48;
+      static_assert(kOut + kF <= kFlag && kFlag < (int)airice::kScalarSlotDoubles, "slot layout");
+      airice::ScalarCall call;
+      if (!call.ok()) return AIRICE_EHIP;
+      airice::ScalarSlot& s = call.slot();
+      std::copy(in, in + 3, s.h);
+      int rc = airice_iceray_launch(model3, s.d, s.d + 1, s.d + 2, 1, s.d + kOut, 1,
+                                    reinterpret_cast<uint8_t*>(s.d + kFlag), s.st);
+      if (rc == AIRICE_OK) rc = call.sync();
+      if (rc) return rc;
+      std::copy(s.h + kOut, s.h + kOut + kF, o);
+      st = *reinterpret_cast<const uint8_t*>(s.h + kFlag);
+    }
+    for (int c = 0; c < kF; ++c) out[(size_t)c * ld] = o[c];
+    if (status) status[0] = st;
+    return AIRICE_OK;
+  }
+  // one device block: z0 | x1 | z1 | out (32 x n) | status
+  DevBuffer buf;
+  HIP_TRY(buf.alloc(sizeof(double) * (3 + kF) * n + n));
+  double* din = static_cast<double*>(buf.p);
+  double* dout = din + 3 * n;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)kF * n);
+  const double* src[3] = {z0, x1, z1};
+  for (int k = 0; k < 3; ++k)
+    HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
+  const int rc = airice_iceray_launch(model3, din, din + n, din + 2 * n, n, dout, n, dst, nullptr);
   if (rc) return rc;
   // the copy-back is on the null stream, like the launch: it waits for the kernel
   HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,

@@ -484,6 +484,47 @@ class AirIceSolver:
         out[4] = np.where(flipped, 180 - out[4], out[4])
         return out, st, flipped
 
+    # ------------------------------------------------------------------ in-ice rays, batched
+    @staticmethod
+    def _ice_model(model):
+        """(A, B, C) as the three host doubles the C-ABI reads, or None for the defaults."""
+        if model is None:
+            return None
+        m = np.ascontiguousarray(model, dtype=np.float64).ravel()
+        if m.size != 3:
+            raise ValueError(f"ice model: (A, B, C), got {m.size} values")
+        return m
+
+    def ice_rays_device(self, z0, x1, z1, out, status=None, ld: int | None = None, stream=None,
+                        model=None) -> None:
+        """airice_iceray_launch: IceRayTracing::IceRayTracing -- the direct, reflected and
+        refracted rays between a transmitter at depth ``z0`` and a receiver ``x1`` metres away at
+        depth ``z1`` (both negative, in the ice) -- for n pairs in one launch.  ``z0``, ``x1``,
+        ``z1`` (n float64 each), ``out`` (32 x ld float64: the _lib.ICERAY_* columns) and
+        ``status`` (n uint8, optional: the _lib.ICERAY_D / _R / _RA0 / _RA1 / _NONFINITE bits)
+        are device tensors; ``model`` is (A, B, C) of n(z) = A + B exp(-C|z|) on the host, the
+        reference's 1.78, -0.43, 0.0132 when None.  Stream-ordered."""
+        n = int(z0.numel())
+        m = self._ice_model(model)
+        check(lib().airice_iceray_launch(ptr(m), ptr(z0), ptr(x1), ptr(z1), n, ptr(out),
+                                         n if ld is None else ld, ptr(status),
+                                         _stream_handle(stream)), "airice_iceray_launch")
+
+    def ice_rays_host(self, z0, x1, z1, model=None):
+        """airice_iceray_host: numpy in, numpy out; the three inputs broadcast against each other.
+        Returns (out (32, n), status (n) uint8).  One pair runs where scalar_mode() says (the
+        calling thread by default); more are copied to the GPU, solved in one launch and copied
+        back."""
+        arrs = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in (z0, x1, z1)])
+        a, b, c = [np.ascontiguousarray(v).ravel() for v in arrs]
+        n = a.size
+        out = np.empty((_lib.ICERAY_FIELDS, n), dtype=np.float64)
+        st = np.empty(n, dtype=np.uint8)
+        m = self._ice_model(model)
+        check(lib().airice_iceray_host(ptr(m), ptr(a), ptr(b), ptr(c), n, ptr(out), max(n, 1),
+                                       ptr(st)), "airice_iceray_host")
+        return out, st
+
     # ------------------------------------------------------------------ pythonwrapper
     def trace_ice_to_air_device(self, depth, ice, txh, dist, out10, stream=None) -> None:
         n = int(depth.numel())

@@ -1,0 +1,92 @@
+/* IceRayTracing.hh -- drop-in for the reference's IceRayTracing:: namespace (IceRayTracing.hh /
+ * IceRayTracing.cc): the in-ice tracer that finds the direct, reflected and refracted rays between
+ * a transmitter and a receiver that are both in the firn.  Served by libairice.so; needs no GSL.
+ *
+ * Same names, signatures, units and output layouts as the reference:
+ *   - SetA / SetB / SetC set the ice model n(z) = A + B exp(-C|z|) for every later call; A_ice,
+ *     B_ice and C_ice are one shared copy here (header statics in the reference).
+ *   - GetDirectRayPar, GetReflectedRayPar, GetRefractedRayPar and IceRayTracing return
+ *     new double[6 / 11 / 22 / 29]; the caller delete[]s them, as with the reference.
+ *   - fDnfR, fDnfR_L, ftimeD, fpathD, fDa, fRa, fRaa keep their (double, void*) signatures and
+ *     parameter structs, so they plug into a caller's own gsl_function.  The residuals read their
+ *     `a` field as the model's A, which is what every caller in the reference passes.
+ *   - Every scalar call runs on the calling CPU thread (the solver's host route, bit for bit
+ *     airice_iceray_host with n = 1).  IceRayTracingBatch is the batch entry: n pairs in one
+ *     launch of iceray_kernel (airice_iceray_host, include/airice.h).
+ * Differences from the reference, all recorded in DESIGN.md §8: TransitionBoundary is 0 and its
+ * dead branches are not carried; GetZmax is the closed form ln(B/(L-A))/C (-1000 where the
+ * reference's bracket [0, 5000] holds no root); receive and incidence angles are asin(L/n(z));
+ * the index just below a turning depth is taken as L + (L-A) expm1(-C 1e-7), without the
+ * reference's cancellation in n(zmax + 1e-7)^2 - L^2;
+ * IceRayTracing's output[12..17] are 0.0, not uninitialised, when their ray failed.
+ * Not provided: attenuation, the _Cnz and _Air variants, DirectRayTracer, MakeTable and its
+ * interpolation, the GetFull*RayPath samplers, and FindFunctionRoot* with GSL-typed arguments.
+ * Link: -L<repo>/airiceraytracing_amd -lairice. */
+#ifndef AIRICE_ICERAYTRACING_HH_
+#define AIRICE_ICERAYTRACING_HH_
+
+#include <stddef.h>
+
+#include "airice.h"
+
+namespace IceRayTracing {
+
+static constexpr double pi = 3.14159265359;       /* IceRayTracing.hh:47 */
+static constexpr double c_light_ms = 299792458;   /* .hh:49 */
+static const double A_ice_def = 1.78;             /* .hh:52-54 */
+static const double B_ice_def = -0.43;
+static const double C_ice_def = 0.0132;
+static constexpr double TransitionBoundary = 0;   /* .hh:55 */
+
+extern double A_ice;
+extern double B_ice;
+extern double C_ice;
+
+void SetA(double &A);
+void SetB(double &B);
+void SetC(double &C);
+double GetB(double z);
+double GetC(double z);
+double Getnz(double z);
+
+/* Fresnel coefficients at the ice surface seen from the ice: n1 = Getnz(0), n2 = 1 (air). */
+double Refl_S(double thetai);
+double Trans_S(double thetai);
+double Refl_P(double thetai);
+double Trans_P(double thetai);
+
+double GetZmax(double A, double L);
+
+struct fDnfR_params { double a, b, c, l; };
+double fDnfR(double x, void *params);
+struct fDnfR_L_params { double a, b, c, z; };
+double fDnfR_L(double x, void *params);
+struct ftimeD_params { double a, b, c, speedc, l; };
+double ftimeD(double x, void *params);
+double fpathD(double x, void *params);
+
+struct fDanfRa_params { double a, z0, x1, z1; };
+double fDa(double x, void *params);
+double fRa(double x, void *params);
+double fRaa(double x, void *params);
+
+double *GetDirectRayPar(double z0, double x1, double z1);
+double *GetReflectedRayPar(double z0, double x1, double z1);
+double *GetRefractedRayPar(double z0, double x1, double z1, double LangR, double RangR,
+                           double checkzeroD, double checkzeroR);
+double *IceRayTracing(double x0, double z0, double x1, double z1);
+
+/* n (Tx depth, distance, Rx depth) triples in one kernel launch, with the model SetA / SetB / SetC
+ * left: value c of pair i at out[c*ld + i] (AIRICE_ICERAY_FIELDS columns: the 29 of IceRayTracing,
+ * then status, evaluations, iterations), status (nullable) the AIRICE_ICERAY_* bits.  Host arrays;
+ * returns AIRICE_OK or an AIRICE_E* code (airice_last_error()).  One pair (n = 1) runs where
+ * airice_scalar_mode says. */
+inline int IceRayTracingBatch(const double *z0, const double *x1, const double *z1, size_t n,
+                              double *out, size_t ld, uint8_t *status) {
+  const double model[3] = {A_ice, B_ice, C_ice};
+  return airice_iceray_host(model, z0, x1, z1, n, out, ld, status);
+}
+
+}  // namespace IceRayTracing
+
+#endif /* AIRICE_ICERAYTRACING_HH_ */

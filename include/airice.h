@@ -452,6 +452,56 @@ int airice_air2ice_host(const airice_medium *m, const double *txh, const double 
                         const double *ice, const double *depth, size_t n, double *out, size_t ld,
                         uint8_t *status);
 
+/* --- in-ice rays (IceRayTracing::IceRayTracing, IceRayTracing.cc:1745-1919) ---------------------
+ * The direct, reflected and refracted rays between a transmitter at (0, z0) and a receiver at
+ * (x1, z1), both in the ice (depths negative, metres), for n pairs in ONE launch of iceray_kernel,
+ * one pair per lane: GetDirectRayPar, GetReflectedRayPar and -- when either failed --
+ * GetRefractedRayPar, with the reference's false-position and Newton searches (GSL semantics
+ * restated) and every acceptance decision as written.  Three deliberate departures (DESIGN.md
+ * §8): the turning depth is the closed form ln(B/(L-A))/C, the receive / incidence angles are
+ * asin(L/n(z)), and the index just below a turning depth is formed without cancellation.  model3 = {A, B, C} of n(z) = A + B exp(-C|z|) on the HOST in both entry points
+ * (SetA / SetB / SetC); NULL is 1.78, -0.43, 0.0132.
+ * Value c of pair i lands at d_out[c*ld + i]; columns 0..28 are the reference's output[0..28]:
+ *   0-3 launch angle (deg) of D, R, Ra0, Ra1; 4-7 their times (s); 8-11 their receive angles
+ *   (-1000: no such ray); 12-13, 14-15, 16-17 the two legs' times of R, Ra0, Ra1 (0.0 when the
+ *   ray failed; uninitialised in the reference); 18 incidence angle at the surface; 19-22 the L
+ *   parameters; 23-24 turning depths of Ra0, Ra1; 25-28 geometric paths (m).
+ *   29 status byte as a double, 30 residual evaluations, 31 false-position iterations of the
+ *   direct search.
+ * Status (also d_status, nullable): AIRICE_ICERAY_D / _R / _RA0 / _RA1 set when that ray is
+ * accepted (|checkzero| < 0.5); AIRICE_ICERAY_NONFINITE alone for a NaN or infinite input, whose
+ * columns 0..28 are NaN and for which no search runs.  Every pair terminates (each search is at
+ * most 100 iterations, at most 9 searches per pair).  Pairs are independent: results do not depend
+ * on the batch or its order.
+ * Stream-ordered, no device allocation, exactly one kernel launch; n == 0 is AIRICE_OK and nothing
+ * is launched; a null required pointer or ld < n is AIRICE_EINVAL before any device call, and
+ * airice_last_error() names the argument. */
+#define AIRICE_ICERAY_FIELDS 32
+#define AIRICE_ICERAY_REFERENCE_FIELDS 29
+#define AIRICE_ICERAY_LAUNCH_ANGLE 0
+#define AIRICE_ICERAY_TIME 4
+#define AIRICE_ICERAY_RECEIVE_ANGLE 8
+#define AIRICE_ICERAY_LEG_TIMES 12
+#define AIRICE_ICERAY_INCIDENCE 18
+#define AIRICE_ICERAY_LVALUE 19
+#define AIRICE_ICERAY_ZMAX 23
+#define AIRICE_ICERAY_PATH 25
+#define AIRICE_ICERAY_STATUS 29
+#define AIRICE_ICERAY_EVALS 30
+#define AIRICE_ICERAY_ITERS 31
+#define AIRICE_ICERAY_D 1
+#define AIRICE_ICERAY_R 2
+#define AIRICE_ICERAY_RA0 4
+#define AIRICE_ICERAY_RA1 8
+#define AIRICE_ICERAY_NONFINITE 128
+int airice_iceray_launch(const double *model3, const double *d_z0, const double *d_x1,
+                         const double *d_z1, size_t n, double *d_out, size_t ld,
+                         uint8_t *d_status, void *stream);
+/* The same with every array on the host: n == 1 runs where airice_scalar_mode says (the calling
+ * thread, or the kernel through the one-query slot); n > 1 copies, launches and synchronises. */
+int airice_iceray_host(const double *model3, const double *z0, const double *x1, const double *z1,
+                       size_t n, double *out, size_t ld, uint8_t *status);
+
 /* Device bookkeeping (thin wrappers so ctypes callers need no HIP runtime binding). */
 int airice_device_count(int *count);
 int airice_set_device(int device);
@@ -504,7 +554,8 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * finder), "group_passes" (the batch-wide grouping passes), "out_kernel" (solve_out /
  * hdtip_out / trace_out), "lookup_kernel", "lookup_multi_kernel"
  * (airice_table_lookup_launch_multi), "ray_consts_kernel" and "ray_paths_kernel" (the two
- * kernels of airice_ray_paths_launch), "air2ice_kernel" (airice_air2ice_launch).
+ * kernels of airice_ray_paths_launch), "air2ice_kernel" (airice_air2ice_launch), "iceray_kernel"
+ * (airice_iceray_launch).
  * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -519,7 +570,8 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * "ray_consts_kernel", "ray_paths_kernel" (airice_ray_paths_launch), "lookup_multi_kernel"
  * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel"), "air2ice_kernel"
  * (airice_air2ice_launch; it does not count as "rtf_kernel"), "air_part_kernel" (the fill of a
- * table launch's air record, below; it does not count as "table_kernel").
+ * table launch's air record, below; it does not count as "table_kernel"), "iceray_kernel"
+ * (airice_iceray_launch).
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
