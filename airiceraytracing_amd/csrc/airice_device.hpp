@@ -487,6 +487,20 @@ __device__ __forceinline__ void prefetch_kernargs() {
   __asm__ volatile("" ::"s"(acc));
 }
 
+// Placement of loads and arithmetic (the warm table block): an empty statement that reads its
+// operands, so that they are formed ahead of it -- per-lane values in VGPRs, wave-uniform ones
+// (kernel-argument fields: their scalar loads) in SGPRs -- instead of being sunk to their first
+// use behind a barrier.  No instruction is emitted and no value changes.
+__device__ __forceinline__ void formed_here_v(double a, double b) {
+  __asm__ volatile("" ::"v"(a), "v"(b));
+}
+__device__ __forceinline__ void formed_here_s(const SegConst& S, double a, double b, double c,
+                                              size_t d, const void* p) {
+  __asm__ volatile("" ::"s"(S.Tn), "s"(S.Ty2), "s"(S.TAy), "s"(S.Rn), "s"(S.Ry2), "s"(S.RAy),
+                   "s"(S.ratio), "s"(S.invC), "s"(S.invCc), "s"(S.dCx), "s"(S.dACx), "s"(a),
+                   "s"(b), "s"(c), "s"(d), "s"(p));
+}
+
 __device__ __forceinline__ void signal_done(const Signal& s) {
   if (s.flag == nullptr) return;
   __threadfence_system();

@@ -68,25 +68,28 @@ struct TableArgs {
                               // air_part_kernel, read by the warm table_kernel; else nullptr
 };
 
-// The air record of a launch of n rays: six columns of stride n, 32 B per ray -- vinc and thd_air
-// as doubles (table column 1 is (float)(thd_air + thd_ice), so thd_air keeps its 53 bits), then
-// table columns 3 ((float)(t_air c)), 8 ((float)geo_air), 6 and 7 (the Fresnel coefficients, which
-// read vinc and the ice height's indices only) as the floats the table stores.  Keeping the two
-// Fresnel floats costs 8 B per ray of traffic and saves their ~40 FP64 operations, two square
-// roots and two quotients: cfg2 12.0 against 13.2 us.
+// The air record of a launch of n rays: 32 B per ray in two planes of 16-byte entries, so that a
+// lane moves its ray with two 16-byte accesses (global_load / global_store_dwordx4), each of them
+// contiguous over the wave.  Plane d, double2[n]: {vinc, thd_air} (table column 1 is
+// (float)(thd_air + thd_ice), so thd_air keeps its 53 bits).  Plane f, float4[n], 16 n bytes behind
+// it (16-byte aligned for every n): table columns {3, 8, 6, 7} -- (float)(t_air c), (float)geo_air
+// and the Fresnel coefficients, which read vinc and the ice height's indices only -- as the floats
+// the table stores.  Keeping the two Fresnel floats costs 8 B per ray of traffic and saves their
+// ~40 FP64 operations, two square roots and two quotients: cfg2 12.0 against 13.2 us.
+// Both planes are addressed as a wave-uniform base plus the lane's 32-bit byte offset 16 k (the
+// global_load / global_store saddr form, as table_columns): a record therefore stays below 2^32
+// bytes -- air_part_cached refuses a larger one (the launch then runs the cold kernel), whatever
+// airice_air_cache_limits allows; there is no 64-bit path.
 __host__ __device__ __forceinline__ size_t air_record_bytes(size_t n) { return 32 * n; }
+constexpr size_t kAirRecordMaxBytes = (size_t)1 << 32;  // exclusive
 struct AirRecord {
-  double* vinc;
-  double* thd_air;
-  float* col3;
-  float* col8;
-  float* col6;
-  float* col7;
+  double2* d;  // this ray's {vinc, thd_air}
+  float4* f;   // this ray's {col3, col8, col6, col7}
 };
-__device__ __forceinline__ AirRecord air_record(unsigned char* base, size_t n) {
-  float* f = reinterpret_cast<float*>(base + 16 * n);
-  return AirRecord{reinterpret_cast<double*>(base), reinterpret_cast<double*>(base) + n,
-                   f, f + n, f + 2 * n, f + 3 * n};
+__device__ __forceinline__ AirRecord air_record(unsigned char* base, size_t n, int k) {
+  const uint32_t off = (uint32_t)k * 16u;
+  return AirRecord{reinterpret_cast<double2*>(base + off),
+                   reinterpret_cast<float4*>(base + 16 * n + off)};
 }
 
 // Debug timeline (AIRICE_TABLE_TRACE=<file>, tools/wave_timeline.py): per wave, the 100 MHz
@@ -128,7 +131,9 @@ __device__ __forceinline__ double table_angle(const TableArgs& G, int iang) {
 // the lines they leave dirty in the XCDs' L2s are a visible part of the launch: cfg2 28.9-29.2
 // -> 27.8-28.2 us, the same table (without any table store the kernel takes 25.6 us); at cfg4
 // size plain stores are faster (20.8 against 21.9 ms per build)
-template <bool SC1>
+// COLS: the columns this call stores (bit c: column c); the other arguments are ignored.
+constexpr unsigned kAllColumns = 0x7FFu;
+template <bool SC1, unsigned COLS = kAllColumns>
 __device__ __forceinline__ void table_columns(float* __restrict__ table, size_t ld, int k, float c0,
                                               float c1, float c2, float c3, float c4, float c5,
                                               float c6, float c7, float c8, float c9, float c10) {
@@ -136,6 +141,7 @@ __device__ __forceinline__ void table_columns(float* __restrict__ table, size_t 
   const size_t ldb = ld * sizeof(float);
   const uint32_t off = (uint32_t)k * 4u;
   auto st = [&](int c, float v) {
+    if (!((COLS >> c) & 1u)) return;
     float* p = reinterpret_cast<float*>(tb + c * ldb + off);
     if constexpr (SC1)
       st_agent(p, v);
@@ -195,34 +201,40 @@ __device__ __forceinline__ void table_ray_air(const DevMedium& M, const IceConst
   else
     vs = sin_start((180 - table_angle(G, iang)) * M.d2r);
   const AirPart a = ray_air_part<A1>(M, I, rc, vs, tab, top_hi);
-  const AirRecord R = air_record(G.air, (size_t)G.n);
-  R.vinc[k] = a.vinc;
-  R.thd_air[k] = a.thd_air;
-  R.col3[k] = (float)(a.t_air * kSpeedC);
-  R.col8[k] = (float)a.geo_air;
   double tS, tP;
   fresnel_from_sine(I.n_air_ice, I.n_ice0, I.n_ratio, a.vinc, tS, tP);
-  R.col6[k] = (float)tS;
-  R.col7[k] = (float)tP;
+  const AirRecord R = air_record(G.air, (size_t)G.n, k);
+  *R.d = double2{a.vinc, a.thd_air};
+  *R.f = float4{(float)(a.t_air * kSpeedC), (float)a.geo_air, (float)tS, (float)tP};
 }
 
-// Table ray k from its air record (the warm table_kernel): the ice part on the cached vinc and
-// thd_air; columns 3, 8, 6 and 7 are the cached floats (t_air, geo_air and the Fresnel
-// coefficients enter no other column).
+// Table ray k from its air record (the warm table_kernel).  rd, rf: the ray's two record entries,
+// loaded by the caller ahead of the block's barrier; H, th: the row's Tx height (RowConst::H) and
+// the column's launch angle.
+// Seven of the eleven columns need nothing from the ice segment -- 0 = H, 4 = th, 5 = thd_air and
+// the record's own floats 3, 8, 6, 7 (t_air, geo_air and the Fresnel coefficients enter no other
+// column) -- so they are stored as soon as the record is there, and travel to memory while the
+// wave traces the ice segment; columns 1, 2, 9 and 10 follow it.  The values and their
+// conversions are those of one table_columns call behind ray_ice_part (d[1] = H, d[11] = th,
+// d[3] = thd_air).  The scheduling barrier keeps the early stores ahead of the segment's
+// arithmetic.  log_ratio2's special-value branch (log_ratio_ieee: an exec-masked global load of
+// the log table and a vmcnt(0)) then also waits for the wave's early stores; only rays with NaN or
+// zero radicands take it, none of them in a grid like cfg2.
+constexpr unsigned kWarmEarlyColumns = 0x1F9u;                          // 0, 3, 4, 5, 6, 7, 8
+constexpr unsigned kWarmLateColumns = kAllColumns & ~kWarmEarlyColumns;  // 1, 2, 9, 10
 template <bool SC1>
 __device__ __forceinline__ void table_ray_warm(const DevMedium& M, const IceConsts& I,
-                                               const TableArgs& G, int k,
+                                               const TableArgs& G, int k, double H, double th,
+                                               const double2 rd, const float4 rf,
                                                float* __restrict__ table, const double* tab) {
-  const AirRecord R = air_record(G.air, (size_t)G.n);
-  const double vinc = R.vinc[k], thd_air = R.thd_air[k];
-  const float c3 = R.col3[k], c8 = R.col8[k], c6 = R.col6[k], c7 = R.col7[k];
-  const int r = ray_row(G, k);
-  const double th = table_angle(G, k - r * G.asteps);
-  const double H = row_height(G, G.row0 + r);  // RowConst::H of the row
+  const double vinc = rd.x, thd_air = rd.y;
+  table_columns<SC1, kWarmEarlyColumns>(table, G.ld, k, (float)H, 0.f, 0.f, rf.x, (float)th,
+                                        (float)thd_air, rf.z, rf.w, rf.y, 0.f, 0.f);
+  __builtin_amdgcn_sched_barrier(0);
   double d[18];
   ray_ice_part<false>(M, I, H, th, G.in_ice != 0, vinc, thd_air, 0.0, 0.0, 0.0, d, tab);
-  table_columns<SC1>(table, G.ld, k, (float)d[1], (float)d[2], (float)d[7], c3, (float)d[11],
-                     (float)d[3], c6, c7, c8, (float)d[17], (float)d[13]);
+  table_columns<SC1, kWarmLateColumns>(table, G.ld, k, 0.f, (float)d[2], (float)d[7], 0.f, 0.f,
+                                       0.f, 0.f, 0.f, 0.f, (float)d[17], (float)d[13]);
 }
 
 // Table launch: one ray per lane, ray k = block * 256 + threadIdx.x (each wave's column store one
@@ -249,6 +261,49 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
   RowConst* rows = reinterpret_cast<RowConst*>(smem);
   // the log table (16 B x 2^kLogTableBits) staged in LDS: 16-byte entries, (1 << kLogTableBits) / BS per thread
   __shared__ __align__(16) double s_logtab[1 << kLogTableBits][2];
+  if constexpr (MODE == kTableWarm) {
+    // One round trip to memory ahead of the arithmetic: the thread's log-table entries and,
+    // behind them, its ray's two record entries are all in flight before the first wait; the
+    // ray's row, height and angle (kernel-argument fields only) are formed under them.  The LDS
+    // write then waits for the log-table entries alone (they were issued first), the record is
+    // awaited after the barrier.
+    // (The log table stays in LDS.  Read from global memory instead -- no staging, no barrier --
+    // the two lookups of a ray are vector loads behind its early stores and wait for them: on a
+    // par with this form at 256 and at 64 threads, behind it at 128; without the early stores it
+    // was the faster of the two.  DESIGN.md §5.)
+    constexpr int NT = ((1 << kLogTableBits) + BS - 1) / BS;
+    const int k = (int)block * BS + (int)threadIdx.x;
+    const bool live = k < G.n;
+    constexpr bool whole = (1 << kLogTableBits) % BS == 0;  // every thread stages NT entries
+    double2 e[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const unsigned t = threadIdx.x + j * BS;
+      if (whole || t < (1u << kLogTableBits))
+        e[j] = *reinterpret_cast<const double2*>(&kLogTable[t][0]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // unconditional loads (a lane past the end re-reads the last ray's entries; n >= 1): no
+    // exec-masked block, so the wait ahead of the LDS write can count past them
+    const AirRecord R = air_record(G.air, (size_t)G.n, min(k, G.n - 1));
+    const double2 rd = *R.d;
+    const float4 rf = *R.f;
+    const int r = ray_row(G, k);
+    const double th = table_angle(G, k - r * G.asteps);
+    const double H = row_height(G, G.row0 + r);
+    // formed here, ahead of the barrier, and with them the kernel-argument fields the ice segment
+    // reads (one scalar round trip under the vector loads instead of one behind the barrier)
+    formed_here_v(th, H);
+    formed_here_s(I.iceseg, I.n_ratio, M.A_ice, M.r2d, G.ld, table);
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const unsigned t = threadIdx.x + j * BS;
+      if (whole || t < (1u << kLogTableBits)) *reinterpret_cast<double2*>(&s_logtab[t][0]) = e[j];
+    }
+    __syncthreads();
+    if (live) table_ray_warm<SC1>(M, I, G, k, H, th, rd, rf, table, &s_logtab[0][0]);
+    return;
+  }
 #pragma unroll
   for (unsigned t = threadIdx.x; t < (1u << kLogTableBits); t += BS) {
     s_logtab[t][0] = kLogTable[t][0];
@@ -262,12 +317,6 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
   }
   const int k0 = (int)block * BS;
   const int ke = min(k0 + BS, G.n);  // end of this block's rays
-  if constexpr (MODE == kTableWarm) {
-    __syncthreads();
-    const int k = k0 + (int)threadIdx.x;
-    if (k < G.n) table_ray_warm<SC1>(M, I, G, k, table, &s_logtab[0][0]);
-    return;
-  }
   const int r0 = k0 < ke ? ray_row(G, k0) : 0;
   {
     const int nrows = k0 < ke ? ray_row(G, ke - 1) - r0 + 1 : 0;
@@ -616,7 +665,9 @@ static int air_part_cached(const DevMedium& M, const IceConsts& I, const TableAr
                            hipStream_t st, unsigned char** out) {
   *out = nullptr;
   const size_t bytes = air_record_bytes((size_t)A.n);
-  if (bytes == 0 || bytes > air_cache().entry_cap() || bytes > air_cache().total_cap())
+  // (kAirRecordMaxBytes: the kernels address a record with 32-bit lane offsets, AirRecord)
+  if (bytes == 0 || bytes >= kAirRecordMaxBytes || bytes > air_cache().entry_cap() ||
+      bytes > air_cache().total_cap())
     return AIRICE_OK;  // before the key is built: a launch that is never cached pays nothing
   const double gk[6] = {A.start_h, A.stop_h, A.step_h, A.start_a, A.stop_a, A.step_a};
   const int ik[4] = {A.hsteps, A.asteps, A.row0, rows};

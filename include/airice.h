@@ -596,7 +596,8 @@ int airice_table_cache_stats(int out[6]);
  * airice_air_cache_limits: a record above entry_bytes is never cached, the records of one device
  * hold at most total_bytes (least recently used unpinned records are freed first); a negative
  * value keeps a limit, total_bytes = 0 turns the cache off and drops every unpinned record
- * and key.  Defaults: 320 MiB and 640 MiB;
+ * and key.  A record of 2^32 bytes or more (2^27 rays) is never cached, whatever entry_bytes
+ * says: the kernels address a record with 32-bit offsets.  Defaults: 320 MiB and 640 MiB;
  * AIRICE_AIR_CACHE_MB=<n> in the environment sets the total (0: off). */
 int airice_air_cache_stats(int64_t out[6]);
 int airice_air_cache_limits(int64_t entry_bytes, int64_t total_bytes);
