@@ -170,6 +170,22 @@ ICERAY_ITERS = 31              # false-position iterations of the direct search
 ICERAY_D, ICERAY_R, ICERAY_RA0, ICERAY_RA1 = 1, 2, 4, 8  # status: ray accepted
 ICERAY_NONFINITE = 128         # status: NaN or infinite input, no search
 ICERAY_DEFAULT_MODEL = (1.78, -0.43, 0.0132)  # A, B, C of n(z) = A + B exp(-C|z|)
+# airice_icesol_launch / _host (IceRayTracing::GetRayTracingSolutions, GetFocusingFactor): a column
+# base + k is slot k of the two rays a receiver sees, in order of arrival.
+ICESOL_FIELDS = 18             # AIRICE_ICESOL_FIELDS
+ICESOL_TIME = 0                # 0-1, s
+ICESOL_PATH = 2                # 2-3, m
+ICESOL_LAUNCH_ANGLE = 4        # 4-5, deg
+ICESOL_RECEIVE_ANGLE = 6       # 6-7, deg; -1000 when the slot holds no ray
+ICESOL_IGNORE = 8              # 8-9: IgnoreCh, 1 use the slot, 0 ignore it
+ICESOL_INCIDENCE = 10          # 10-11: IncidenceAngleInIce (100, or the reflected ray's)
+ICESOL_ATTENUATION = 12        # 12-13: AttRay = 1 - A0 * integral of ds / L_att
+ICESOL_RAY_TYPE = 14           # 14-15: 1 D, 2 R, 3 Ra0, 4 Ra1
+ICESOL_FOCUSING = 16           # 16-17: focusing factor (0.0: condition not met, or not asked for)
+ICESOL_SLOT0, ICESOL_SLOT1 = 1, 2      # status: IgnoreCh of the slot
+ICESOL_STRAIGHT = 4            # status: the straight-line rule for equal depths fired
+ICESOL_FOCUS0, ICESOL_FOCUS1 = 8, 16   # status: the factor's condition was met
+ICESOL_NONFINITE = 128         # status: the solver flagged the row non-finite
 
 EXPORTED_SYMBOLS = (
     "airice_last_error", "airice_version", "airice_atmosphere_load", "airice_atmosphere_parse",
@@ -182,7 +198,8 @@ EXPORTED_SYMBOLS = (
     "airice_ray_paths_launch", "airice_ray_paths_host", "airice_trace_ice_to_air_launch",
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
     "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host",
-    "airice_iceray_launch", "airice_iceray_host", "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
+    "airice_iceray_launch", "airice_iceray_host", "airice_icesol_launch", "airice_icesol_host",
+    "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
     "airice_kernel_timing", "airice_kernel_time", "airice_launch_count",
     "airice_table_cache_stats", "airice_air_cache_stats", "airice_air_cache_limits",
@@ -264,6 +281,8 @@ def lib() -> ctypes.CDLL:
         "airice_air2ice_host": ([M, P, P, P, P, S, P, S, P], I),
         "airice_iceray_launch": ([P, P, P, P, S, P, S, P, P], I),
         "airice_iceray_host": ([P, P, P, P, S, P, S, P], I),
+        "airice_icesol_launch": ([P, P, P, P, P, S, P, S, S, D, D, P, S, P, P], I),
+        "airice_icesol_host": ([P, P, P, P, S, D, D, I, P, S, P], I),
         "airice_table_to_host": ([P, S, S, P, S, P], I),
         "airice_host_register": ([P, S], I),
         "airice_host_unregister": ([P], I),

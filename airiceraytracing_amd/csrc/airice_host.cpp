@@ -13,6 +13,7 @@
 #include "airice.h"
 #include "airice_host.h"
 #include "airice_iceray.hpp"
+#include "airice_icesol.hpp"
 
 namespace airice {
 
@@ -262,6 +263,29 @@ void iceray_host_one(const double model[3], const double in[3], double* out32, u
   const iceray::IceModel m = {model[0], model[1], model[2]};
   const uint8_t st = iceray::solve_pair(m, in[0], in[1], in[2], iceray::ArrayOut{out32});
   if (status != nullptr) *status = st;
+}
+
+void icesol_host_one(const double model[3], const double in[3], double a0, double frequency_ghz,
+                     bool focusing, double* out18, uint8_t* status) {
+  const iceray::IceModel m = {model[0], model[1], model[2]};
+  const icesol::Medium q = icesol::make_medium(a0, frequency_ghz);
+  double at[iceray::kColumns], lower[iceray::kColumns];
+  iceray::solve_pair(m, in[0], in[1], in[2], iceray::ArrayOut{at});
+  if (focusing)
+    iceray::solve_pair(m, in[0], in[1], in[2] - icesol::kLowerRx, iceray::ArrayOut{lower});
+  const uint8_t st = icesol::solve_pair(
+      m, q, in[0], in[1], in[2], [&](int c) { return at[c]; }, focusing,
+      [&](int c) { return lower[c]; }, icesol::ArrayOut{out18});
+  if (status != nullptr) *status = st;
+}
+
+const char* icesol_bad_value(const double model[3], double a0, double frequency_ghz) {
+  if (!iceray::is_finite(a0)) return "a0 is not finite";
+  if (!(iceray::is_finite(frequency_ghz) && frequency_ghz > 0))
+    return "frequency_ghz is not finite and positive";
+  if (!(model[1] < 0 && model[2] > 0 && iceray::is_finite(model[1]) && iceray::is_finite(model[2])))
+    return "model3 is outside B < 0 < C";
+  return nullptr;
 }
 
 }  // namespace airice

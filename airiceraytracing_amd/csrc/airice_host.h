@@ -20,5 +20,14 @@ int parse_gdas(const std::string& text, airice_medium* m);
 // One (z0, x1, z1) pair of the in-ice solver on the calling thread (airice_iceray.hpp compiled
 // for the host): model = {A, B, C}, out32 = the AIRICE_ICERAY_FIELDS values, status nullable.
 void iceray_host_one(const double model[3], const double in[3], double* out32, uint8_t* status);
+// GetRayTracingSolutions (and, with focusing, GetFocusingFactor) of one pair on the calling thread
+// (airice_icesol.hpp compiled for the host): the solver's host route for the receiver -- and for
+// the one 1 cm lower -- then the lane function of icesol_kernel.  out18 = the
+// AIRICE_ICESOL_FIELDS values, status nullable.
+void icesol_host_one(const double model[3], const double in[3], double a0, double frequency_ghz,
+                     bool focusing, double* out18, uint8_t* status);
+// The argument checks the icesol entries share: nullptr, or what is wrong with a0, the frequency
+// or the model (a static string for airice_last_error()).
+const char* icesol_bad_value(const double model[3], double a0, double frequency_ghz);
 
 }  // namespace airice

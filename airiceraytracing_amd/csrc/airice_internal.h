@@ -130,6 +130,14 @@ void air2ice_host_one(const DevMedium& M, const double in[4], double* out16, uin
 // lane's function on the calling thread is iceray_host_one (airice_host.h).
 int launch_iceray(const double model[3], const double* z0, const double* x1, const double* z1,
                   size_t n, double* out, size_t ld, uint8_t* status, hipStream_t st);
+// GetRayTracingSolutions / GetFocusingFactor over the solver's rows (airice_icesol.hip):
+// icesol_kernel, one pair per lane, AIRICE_ICESOL_FIELDS columns of stride ld and a status byte
+// (nullable); rays_lower nullable (no focusing).  The lane's function on the calling thread is
+// icesol_host_one (airice_host.h).
+int launch_icesol(const double model[3], double a0, double frequency_ghz, const double* z0,
+                  const double* x1, const double* z1, const double* rays, size_t ld_rays,
+                  const double* rays_lower, size_t ld_lower, size_t n, double* out, size_t ld,
+                  uint8_t* status, hipStream_t st);
 
 static_assert(kMaxParsedLayers == kMaxLayers, "parse and kernels agree on the layer count");
 
@@ -199,6 +207,7 @@ enum KTimerId {
   KT_LOOKUP_MULTI,
   KT_AIR2ICE,
   KT_ICERAY,
+  KT_ICESOL,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -229,6 +238,7 @@ enum LaunchId {
   LC_AIR2ICE,       // air2ice_kernel (batched GSL-Brent point-to-point solve)
   LC_AIR_PART,      // air_part_kernel (fills a table launch's air record)
   LC_ICERAY,        // iceray_kernel (batched in-ice direct / reflected / refracted solve)
+  LC_ICESOL,        // icesol_kernel (the two rays a receiver sees, attenuation, focusing)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

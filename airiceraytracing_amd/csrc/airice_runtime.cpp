@@ -206,14 +206,17 @@ static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kerne
                                                "group_passes",      "out_kernel",
                                                "lookup_kernel",     "ray_consts_kernel",
                                                "ray_paths_kernel",  "lookup_multi_kernel",
-                                               "air2ice_kernel",    "iceray_kernel"};
+                                               "air2ice_kernel",    "iceray_kernel",
+                                               "icesol_kernel"};
+static_assert(sizeof(kKtNames) / sizeof(kKtNames[0]) == KT_COUNT, "one name per timer");
 
 std::atomic<long long> g_launches[LC_COUNT];
 static const char* const kLcNames[LC_COUNT] = {
     "table_kernel",        "rays_kernel",  "scalar_ray_kernel", "roots_kernel",
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
-    "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel", "iceray_kernel"};
+    "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel", "iceray_kernel",
+    "icesol_kernel"};
 static_assert(sizeof(kLcNames) / sizeof(kLcNames[0]) == LC_COUNT, "one name per counter");
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
@@ -1184,6 +1187,125 @@ int airice_iceray_host(const double* model3, const double* z0, const double* x1,
   const int rc = airice_iceray_launch(model3, din, din + n, din + 2 * n, n, dout, n, dst, nullptr);
   if (rc) return rc;
   // the copy-back is on the null stream, like the launch: it waits for the kernel
+  HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
+                      hipMemcpyDeviceToHost));
+  if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
+  return AIRICE_OK;
+}
+
+// ---- GetRayTracingSolutions / GetFocusingFactor over the solver's rows --------------------------
+// What is wrong with the values of an icesol call (set as the error), or false.
+static bool icesol_refuses(const double* model3, double a0, double frequency_ghz) {
+  const char* bad = airice::icesol_bad_value(model3 != nullptr ? model3 : kIceRayDefaultModel, a0,
+                                             frequency_ghz);
+  if (bad != nullptr) set_error("icesol: %s", bad);
+  return bad != nullptr;
+}
+
+int airice_icesol_launch(const double* model3, const double* d_z0, const double* d_x1,
+                         const double* d_z1, const double* d_rays, size_t ld_rays,
+                         const double* d_rays_lower, size_t ld_lower, size_t n, double a0,
+                         double frequency_ghz, double* d_out, size_t ld, uint8_t* d_status,
+                         void* stream) {
+  if (n == 0) return AIRICE_OK;
+  const char* a = iceray_null_arg(d_z0, d_x1, d_z1, d_out);
+  if (a == nullptr && d_rays == nullptr) a = "rays";
+  if (a != nullptr) {
+    set_error("icesol: null argument (%s)", a);
+    return AIRICE_EINVAL;
+  }
+  if (ld < n || ld_rays < n || (d_rays_lower != nullptr && ld_lower < n)) {
+    set_error("icesol: %s (%zu) < n (%zu)", ld < n ? "ld" : ld_rays < n ? "ld_rays" : "ld_lower",
+              ld < n ? ld : ld_rays < n ? ld_rays : ld_lower, n);
+    return AIRICE_EINVAL;
+  }
+  if (icesol_refuses(model3, a0, frequency_ghz)) return AIRICE_EINVAL;
+  if (n > (size_t)0x7fffffff * 256) {
+    set_error("icesol: n = %zu exceeds one launch", n);
+    return AIRICE_EINVAL;
+  }
+  const int rc = airice::launch_icesol(model3 != nullptr ? model3 : kIceRayDefaultModel, a0,
+                                       frequency_ghz, d_z0, d_x1, d_z1, d_rays, ld_rays,
+                                       d_rays_lower, ld_lower, n, d_out, ld, d_status,
+                                       (hipStream_t)stream);
+  if (rc) set_error("icesol launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return rc;
+}
+
+int airice_icesol_host(const double* model3, const double* z0, const double* x1, const double* z1,
+                       size_t n, double a0, double frequency_ghz, int focusing, double* out,
+                       size_t ld, uint8_t* status) {
+  if (n == 0) return AIRICE_OK;
+  if (const char* a = iceray_null_arg(z0, x1, z1, out)) {
+    set_error("icesol: null argument (%s)", a);
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("icesol: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  if (icesol_refuses(model3, a0, frequency_ghz)) return AIRICE_EINVAL;
+  constexpr int kF = AIRICE_ICESOL_FIELDS, kR = AIRICE_ICERAY_FIELDS;
+  const bool focus = focusing != 0;
+  if (n == 1) {  // one pair: where airice_scalar_mode says
+    const double in[3] = {z0[0], x1[0], z1[0]};
+    double o[kF];
+    uint8_t st = 0;
+    if (airice::scalar_on_host()) {
+      airice::icesol_host_one(model3 != nullptr ? model3 : kIceRayDefaultModel, in, a0,
+                              frequency_ghz, focus, o, &st);
+    } else {
+      // the scalar slot: z0, x1, z1 and the lower z1 at h[0..3], the receiver's 32 columns from
+      // h[8], the lower receiver's from h[40], the 18 outputs from h[72], the status byte at h + 96
+      constexpr int kRays = 8, kLower = kRays + kR, kOut = kLower + kR, kFlag = 96;
+      static_assert(kOut + kF <= kFlag && kFlag < (int)airice::kScalarSlotDoubles, "slot layout");
+      airice::ScalarCall call;
+      if (!call.ok()) return AIRICE_EHIP;
+      airice::ScalarSlot& s = call.slot();
+      std::copy(in, in + 3, s.h);
+      s.h[3] = in[2] - 0.01;
+      int rc = airice_iceray_launch(model3, s.d, s.d + 1, s.d + 2, 1, s.d + kRays, 1, nullptr, s.st);
+      if (rc == AIRICE_OK && focus)
+        rc = airice_iceray_launch(model3, s.d, s.d + 1, s.d + 3, 1, s.d + kLower, 1, nullptr, s.st);
+      if (rc == AIRICE_OK)
+        rc = airice_icesol_launch(model3, s.d, s.d + 1, s.d + 2, s.d + kRays, 1,
+                                  focus ? s.d + kLower : nullptr, 1, 1, a0, frequency_ghz,
+                                  s.d + kOut, 1, reinterpret_cast<uint8_t*>(s.d + kFlag), s.st);
+      if (rc == AIRICE_OK) rc = call.sync();
+      if (rc) return rc;
+      std::copy(s.h + kOut, s.h + kOut + kF, o);
+      st = *reinterpret_cast<const uint8_t*>(s.h + kFlag);
+    }
+    for (int c = 0; c < kF; ++c) out[(size_t)c * ld] = o[c];
+    if (status) status[0] = st;
+    return AIRICE_OK;
+  }
+  // one device block: z0 | x1 | z1 | z1 - 0.01 | rays (32 x n) | lower rays (32 x n) | out
+  // (18 x n) | status
+  const size_t n_rays = focus ? 2 : 1;
+  DevBuffer buf;
+  HIP_TRY(buf.alloc(sizeof(double) * (4 + n_rays * kR + kF) * n + n));
+  double* din = static_cast<double*>(buf.p);
+  double* drays = din + 4 * n;
+  double* dlower = focus ? drays + (size_t)kR * n : nullptr;
+  double* dout = drays + n_rays * kR * n;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)kF * n);
+  const double* src[3] = {z0, x1, z1};
+  for (int k = 0; k < 3; ++k)
+    HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
+  int rc = airice_iceray_launch(model3, din, din + n, din + 2 * n, n, drays, n, nullptr, nullptr);
+  if (rc) return rc;
+  if (focus) {
+    std::vector<double> lower(z1, z1 + n);
+    for (double& v : lower) v = v - 0.01;
+    HIP_TRY(hipMemcpy(din + 3 * n, lower.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    rc = airice_iceray_launch(model3, din, din + n, din + 3 * n, n, dlower, n, nullptr, nullptr);
+    if (rc) return rc;
+  }
+  rc = airice_icesol_launch(model3, din, din + n, din + 2 * n, drays, n, dlower, n, n, a0,
+                            frequency_ghz, dout, n, dst, nullptr);
+  if (rc) return rc;
+  // the copy-back is on the null stream, like the launches: it waits for the kernels
   HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
                       hipMemcpyDeviceToHost));
   if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));

@@ -2,7 +2,8 @@
 // names and signatures over the in-ice solver of airice_iceray.hpp.  Every call here runs on the
 // calling thread: IceRayTracing() is the solver's host route (iceray_host_one, the function
 // airice_iceray_host runs for n = 1), the *RayPar functions and the (double, void*) functions are
-// the same header's pieces.  No HIP here, so this file also builds into the sanitizer driver
+// the same header's pieces; GetRayTracingSolutions and GetFocusingFactor are icesol_host_one (the
+// function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's.  No HIP here, so this file also builds into the sanitizer driver
 // (tests/cpp/iceray_driver.cpp, `make iceray_asan`).
 #include <algorithm>
 #include <cmath>
@@ -10,8 +11,10 @@
 #include "IceRayTracing.hh"
 #include "airice_host.h"
 #include "airice_iceray.hpp"
+#include "airice_icesol.hpp"
 
 namespace ir = airice::iceray;
+namespace is = airice::icesol;
 
 namespace IceRayTracing {
 
@@ -165,6 +168,67 @@ double *IceRayTracing(double /*x0*/, double z0, double x1, double z1) {
   double *output = new double[AIRICE_ICERAY_REFERENCE_FIELDS];
   for (int c = 0; c < AIRICE_ICERAY_REFERENCE_FIELDS; c++) output[c] = all[c];
   return output;
+}
+
+double GetIceTemperature(double z) { return is::ice_temperature(z); }
+double GetIceAttenuationLength(double z, double frequency) {
+  return is::attenuation_length(z, frequency);
+}
+
+// AttenuationIntegrand (.cc:166-176) as written: params = {A0, frequency, L}
+double AttenuationIntegrand(double x, void *params) {
+  const double *p = static_cast<const double *>(params);
+  return (p[0] / GetIceAttenuationLength(x, p[1])) *
+         std::sqrt(1 + std::pow(std::tan(std::asin(p[2] / Getnz(x))), 2));
+}
+
+// The integral of it between the limits given, by the solver's fixed rule (no GSL workspace)
+double IntegrateOverLAttn(double A0, double Frequency, double z0, double z1, double Lvalue) {
+  return is::attenuation_between(model(), is::make_medium(A0, Frequency), z0, z1, Lvalue);
+}
+double GetTotalAttenuationDirect(double A0, double frequency, double z0, double z1,
+                                 double Lvalue) {
+  return is::total_attenuation(model(), is::make_medium(A0, frequency), 1, z0, z1, Lvalue);
+}
+double GetTotalAttenuationReflected(double A0, double frequency, double z0, double z1,
+                                    double Lvalue) {
+  return is::total_attenuation(model(), is::make_medium(A0, frequency), 2, z0, z1, Lvalue);
+}
+// zmax is not read: each leg ends at the turning depth of Lvalue itself
+double GetTotalAttenuationRefracted(double A0, double frequency, double z0, double z1,
+                                    double /*zmax*/, double Lvalue) {
+  return is::total_attenuation(model(), is::make_medium(A0, frequency), 3, z0, z1, Lvalue);
+}
+
+void GetRayTracingSolutions(double RxDepth, double Distance, double TxDepth, double TimeRay[2],
+                            double PathRay[2], double LaunchAngle[2], double RecieveAngle[2],
+                            int IgnoreCh[2], double IncidenceAngleInIce[2], double A0,
+                            double frequency, double AttRay[2]) {
+  const double m[3] = {A_ice, B_ice, C_ice};
+  const double in[3] = {TxDepth, Distance, RxDepth};
+  double o[AIRICE_ICESOL_FIELDS];
+  airice::icesol_host_one(m, in, A0, frequency, false, o, nullptr);
+  for (int k = 0; k < 2; k++) {
+    TimeRay[k] = o[AIRICE_ICESOL_TIME + k];
+    PathRay[k] = o[AIRICE_ICESOL_PATH + k];
+    LaunchAngle[k] = o[AIRICE_ICESOL_LAUNCH_ANGLE + k];
+    RecieveAngle[k] = o[AIRICE_ICESOL_RECEIVE_ANGLE + k];
+    IgnoreCh[k] = (int)o[AIRICE_ICESOL_IGNORE + k];
+    IncidenceAngleInIce[k] = o[AIRICE_ICESOL_INCIDENCE + k];
+    AttRay[k] = o[AIRICE_ICESOL_ATTENUATION + k];
+  }
+}
+
+// A factor whose condition is not met stays what the caller left there, as in the reference
+void GetFocusingFactor(double zT, double xR, double zR, double focusing[2]) {
+  const double m[3] = {A_ice, B_ice, C_ice};
+  const double in[3] = {zT, xR, zR};
+  double o[AIRICE_ICESOL_FIELDS];
+  uint8_t st = 0;
+  airice::icesol_host_one(m, in, 1, 0.1, true, o, &st);
+  if (st & AIRICE_ICESOL_FOCUS0) focusing[0] = o[AIRICE_ICESOL_FOCUSING];
+  if (st & AIRICE_ICESOL_FOCUS1) focusing[1] = o[AIRICE_ICESOL_FOCUSING + 1];
+  if (zR == zT && focusing[0] == 0) focusing[0] = 1.;
 }
 
 }  // namespace IceRayTracing

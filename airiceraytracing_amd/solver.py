@@ -525,6 +525,41 @@ class AirIceSolver:
                                        ptr(st)), "airice_iceray_host")
         return out, st
 
+    def ice_solutions_device(self, z0, x1, z1, rays, out, status=None, a0: float = 1.0,
+                             frequency: float = 0.1, rays_lower=None, ld: int | None = None,
+                             stream=None, model=None) -> None:
+        """airice_icesol_launch: IceRayTracing::GetRayTracingSolutions -- the two rays a receiver
+        sees, in order of arrival, with their ice attenuation -- for n pairs in one launch over
+        ``rays``, the (32, ld_rays) tensor ``ice_rays_device`` wrote for the same ``z0``, ``x1``,
+        ``z1``.  With ``rays_lower`` (what it wrote for ``z1 - 0.01``) also GetFocusingFactor.
+        ``out`` (18 x ld float64: the _lib.ICESOL_* columns) and ``status`` (n uint8, optional:
+        the _lib.ICESOL_* bits) are device tensors; ``a0`` and ``frequency`` (GHz) hold for the
+        batch; ``model`` as ``ice_rays_device``.  Stream-ordered."""
+        n = int(z0.numel())
+        m = self._ice_model(model)
+        check(lib().airice_icesol_launch(
+            ptr(m), ptr(z0), ptr(x1), ptr(z1), ptr(rays), int(rays.stride(0)), ptr(rays_lower),
+            0 if rays_lower is None else int(rays_lower.stride(0)), n, float(a0),
+            float(frequency), ptr(out), n if ld is None else ld, ptr(status),
+            _stream_handle(stream)), "airice_icesol_launch")
+
+    def ice_solutions_host(self, z0, x1, z1, a0: float = 1.0, frequency: float = 0.1,
+                           focusing: bool = False, model=None):
+        """airice_icesol_host: numpy in, numpy out; the three inputs broadcast against each other.
+        Returns (out (18, n), status (n) uint8).  One pair runs where scalar_mode() says (the
+        calling thread by default); more are copied to the GPU, solved (iceray_kernel once, twice
+        with ``focusing``, then icesol_kernel once) and copied back."""
+        arrs = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in (z0, x1, z1)])
+        a, b, c = [np.ascontiguousarray(v).ravel() for v in arrs]
+        n = a.size
+        out = np.empty((_lib.ICESOL_FIELDS, n), dtype=np.float64)
+        st = np.empty(n, dtype=np.uint8)
+        m = self._ice_model(model)
+        check(lib().airice_icesol_host(ptr(m), ptr(a), ptr(b), ptr(c), n, float(a0),
+                                       float(frequency), 1 if focusing else 0, ptr(out),
+                                       max(n, 1), ptr(st)), "airice_icesol_host")
+        return out, st
+
     # ------------------------------------------------------------------ pythonwrapper
     def trace_ice_to_air_device(self, depth, ice, txh, dist, out10, stream=None) -> None:
         n = int(depth.numel())

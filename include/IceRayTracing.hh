@@ -19,7 +19,17 @@
  * the index just below a turning depth is taken as L + (L-A) expm1(-C 1e-7), without the
  * reference's cancellation in n(zmax + 1e-7)^2 - L^2;
  * IceRayTracing's output[12..17] are 0.0, not uninitialised, when their ray failed.
- * Not provided: attenuation, the _Cnz and _Air variants, DirectRayTracer, MakeTable and its
+ *   - GetRayTracingSolutions and GetFocusingFactor are the reference's statements over that
+ *     solver (bit for bit airice_icesol_host with n = 1); GetRayTracingSolutionsBatch is their
+ *     batch entry (iceray_kernel once or twice, then icesol_kernel once).  The attenuation
+ *     (DESIGN.md §9): IntegrateOverLAttn is a fixed 24-node Gauss-Legendre rule after the
+ *     substitution z = zv + s^2, where the reference calls gsl_integration_qags at epsrel 1e-7
+ *     (the rule is within 1e-9 of the integral); GetTotalAttenuationRefracted ends each leg at
+ *     the turning depth of Lvalue itself and does not read zmax; a limit above the depth where
+ *     n = L, or L >= A, gives NaN; GetIceTemperature is the cubic in Horner form.  It needs
+ *     B < 0 < C.  A NaN or infinite input of GetRayTracingSolutions gives NaN values with
+ *     IgnoreCh 0.
+ * Not provided: the _Cnz and _Air variants, DirectRayTracer, MakeTable and its
  * interpolation, the GetFull*RayPath samplers, and FindFunctionRoot* with GSL-typed arguments.
  * Link: -L<repo>/airiceraytracing_amd -lairice. */
 #ifndef AIRICE_ICERAYTRACING_HH_
@@ -76,6 +86,25 @@ double *GetRefractedRayPar(double z0, double x1, double z1, double LangR, double
                            double checkzeroD, double checkzeroR);
 double *IceRayTracing(double x0, double z0, double x1, double z1);
 
+/* Ice temperature (C) and attenuation length (m) at depth z, frequency in GHz (.cc:134-163) */
+double GetIceTemperature(double z);
+double GetIceAttenuationLength(double z, double frequency);
+/* params = double[3] {A0, frequency, L} */
+double AttenuationIntegrand(double x, void *params);
+double IntegrateOverLAttn(double A0, double Frequency, double z0, double z1, double Lvalue);
+double GetTotalAttenuationDirect(double A0, double frequency, double z0, double z1, double Lvalue);
+double GetTotalAttenuationReflected(double A0, double frequency, double z0, double z1,
+                                    double Lvalue);
+double GetTotalAttenuationRefracted(double A0, double frequency, double z0, double z1, double zmax,
+                                    double Lvalue);
+
+/* The two rays a receiver sees, ordered by arrival time (.cc:2907-3210) */
+void GetRayTracingSolutions(double RxDepth, double Distance, double TxDepth, double TimeRay[2],
+                            double PathRay[2], double LaunchAngle[2], double RecieveAngle[2],
+                            int IgnoreCh[2], double IncidenceAngleInIce[2], double A0,
+                            double frequency, double AttRay[2]);
+void GetFocusingFactor(double zT, double xR, double zR, double focusing[2]);
+
 /* n (Tx depth, distance, Rx depth) triples in one kernel launch, with the model SetA / SetB / SetC
  * left: value c of pair i at out[c*ld + i] (AIRICE_ICERAY_FIELDS columns: the 29 of IceRayTracing,
  * then status, evaluations, iterations), status (nullable) the AIRICE_ICERAY_* bits.  Host arrays;
@@ -85,6 +114,19 @@ inline int IceRayTracingBatch(const double *z0, const double *x1, const double *
                               double *out, size_t ld, uint8_t *status) {
   const double model[3] = {A_ice, B_ice, C_ice};
   return airice_iceray_host(model, z0, x1, z1, n, out, ld, status);
+}
+
+/* GetRayTracingSolutions -- and, with focusing != 0, GetFocusingFactor -- of n (Tx depth,
+ * distance, Rx depth) triples: value c of pair i at out[c*ld + i] (AIRICE_ICESOL_FIELDS columns),
+ * status (nullable) the AIRICE_ICESOL_* bits (airice_icesol_host, include/airice.h).  A0 and the
+ * frequency (GHz) hold for the batch; a focusing factor whose condition is not met is 0.0. */
+inline int GetRayTracingSolutionsBatch(const double *TxDepth, const double *Distance,
+                                       const double *RxDepth, size_t n, double A0,
+                                       double frequency, int focusing, double *out, size_t ld,
+                                       uint8_t *status) {
+  const double model[3] = {A_ice, B_ice, C_ice};
+  return airice_icesol_host(model, TxDepth, Distance, RxDepth, n, A0, frequency, focusing, out,
+                            ld, status);
 }
 
 }  // namespace IceRayTracing

@@ -502,6 +502,62 @@ int airice_iceray_launch(const double *model3, const double *d_z0, const double 
 int airice_iceray_host(const double *model3, const double *z0, const double *x1, const double *z1,
                        size_t n, double *out, size_t ld, uint8_t *status);
 
+/* --- the two rays a receiver sees (IceRayTracing::GetRayTracingSolutions, IceRayTracing.cc:
+ * 2907-3210) and their focusing factors (GetFocusingFactor, .cc:3218-3293) ----------------------
+ * For n pairs in ONE launch of icesol_kernel, one pair per lane, over the rows airice_iceray_launch
+ * wrote: d_rays (32 columns of stride ld_rays) for (d_z0, d_x1, d_z1) and -- nullable; NULL means
+ * no focusing -- d_rays_lower (stride ld_lower) for (d_z0, d_x1, d_z1 - 0.01).  The choice of the
+ * two rays, IgnoreCh, the swap by arrival time and the straight-line rule for equal depths are
+ * the reference's statements as written; the ice attenuation along each chosen ray is
+ * AttRay = 1 - a0 * integral of ds / L_att(z, frequency_ghz) (GetTotalAttenuation*, .cc:134-219).
+ * Departures: the integral is a fixed 24-node Gauss-Legendre rule in
+ * s = sqrt(z - zv), zv = ln(B/(L-A))/C, where the reference calls QAGS at epsrel 1e-7; a refracted
+ * leg ends at the turning depth of its own L, not at the reported zmax; a leg on which the
+ * reference's integrand is NaN somewhere gives NaN.
+ * Value c of pair i lands at d_out[c*ld + i], slot 0 then slot 1 in each pair of columns:
+ *   0-1 time (s), 2-3 geometric path (m), 4-5 launch angle (deg), 6-7 receive angle (deg; -1000:
+ *   no ray), 8-9 IgnoreCh (1: use the slot, 0: ignore it), 10-11 IncidenceAngleInIce (100, or the
+ *   reflected ray's; not swapped), 12-13 AttRay, 14-15 RayType (1 D, 2 R, 3 Ra0, 4 Ra1; computed
+ *   and dropped by the reference), 16-17 focusing factor (0.0 where its condition is not met or
+ *   d_rays_lower is NULL).
+ * Status (also d_status, nullable): AIRICE_ICESOL_SLOT0 / _SLOT1 = IgnoreCh of the slot,
+ * _STRAIGHT the straight-line rule fired, _FOCUS0 / _FOCUS1 the focusing factor's condition was met and its
+ * formula set it (the closing rule, zR == zT and factor 0 == 0 -> 1, sets no bit), _NONFINITE alone for a row the solver flagged
+ * AIRICE_ICERAY_NONFINITE, whose value columns are NaN and whose IgnoreCh and types are 0.
+ * model3 as airice_iceray_launch; it must have B < 0 < C.  Pairs are independent.
+ * Stream-ordered, no device allocation, exactly one kernel launch; n == 0 is AIRICE_OK and nothing
+ * is launched.  AIRICE_EINVAL before any device call, with airice_last_error() naming the
+ * argument: a null required pointer; ld, ld_rays or (with d_rays_lower) ld_lower < n; a non-finite
+ * a0; a frequency_ghz that is not finite and positive; a model outside B < 0 < C. */
+#define AIRICE_ICESOL_FIELDS 18
+#define AIRICE_ICESOL_TIME 0
+#define AIRICE_ICESOL_PATH 2
+#define AIRICE_ICESOL_LAUNCH_ANGLE 4
+#define AIRICE_ICESOL_RECEIVE_ANGLE 6
+#define AIRICE_ICESOL_IGNORE 8
+#define AIRICE_ICESOL_INCIDENCE 10
+#define AIRICE_ICESOL_ATTENUATION 12
+#define AIRICE_ICESOL_RAY_TYPE 14
+#define AIRICE_ICESOL_FOCUSING 16
+#define AIRICE_ICESOL_SLOT0 1
+#define AIRICE_ICESOL_SLOT1 2
+#define AIRICE_ICESOL_STRAIGHT 4
+#define AIRICE_ICESOL_FOCUS0 8
+#define AIRICE_ICESOL_FOCUS1 16
+#define AIRICE_ICESOL_NONFINITE 128
+int airice_icesol_launch(const double *model3, const double *d_z0, const double *d_x1,
+                         const double *d_z1, const double *d_rays, size_t ld_rays,
+                         const double *d_rays_lower, size_t ld_lower, size_t n, double a0,
+                         double frequency_ghz, double *d_out, size_t ld, uint8_t *d_status,
+                         void *stream);
+/* The whole of it with every array on the host; focusing != 0 also solves the receivers 1 cm
+ * lower.  n > 1: copies, iceray_kernel once per receiver set (once or twice), icesol_kernel once,
+ * synchronises.  n == 1 runs where airice_scalar_mode says (the calling thread, or the same
+ * kernels through the one-query slot). */
+int airice_icesol_host(const double *model3, const double *z0, const double *x1, const double *z1,
+                       size_t n, double a0, double frequency_ghz, int focusing, double *out,
+                       size_t ld, uint8_t *status);
+
 /* Device bookkeeping (thin wrappers so ctypes callers need no HIP runtime binding). */
 int airice_device_count(int *count);
 int airice_set_device(int device);
@@ -555,7 +611,7 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * hdtip_out / trace_out), "lookup_kernel", "lookup_multi_kernel"
  * (airice_table_lookup_launch_multi), "ray_consts_kernel" and "ray_paths_kernel" (the two
  * kernels of airice_ray_paths_launch), "air2ice_kernel" (airice_air2ice_launch), "iceray_kernel"
- * (airice_iceray_launch).
+ * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch).
  * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -571,7 +627,7 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel"), "air2ice_kernel"
  * (airice_air2ice_launch; it does not count as "rtf_kernel"), "air_part_kernel" (the fill of a
  * table launch's air record, below; it does not count as "table_kernel"), "iceray_kernel"
- * (airice_iceray_launch).
+ * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch).
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
