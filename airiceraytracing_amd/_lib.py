@@ -186,6 +186,16 @@ ICESOL_SLOT0, ICESOL_SLOT1 = 1, 2      # status: IgnoreCh of the slot
 ICESOL_STRAIGHT = 4            # status: the straight-line rule for equal depths fired
 ICESOL_FOCUS0, ICESOL_FOCUS1 = 8, 16   # status: the factor's condition was met
 ICESOL_NONFINITE = 128         # status: the solver flagged the row non-finite
+# airice_icetab_* (IceRayTracing::MakeTable / GetInterpolatedValue): the image's layout and the
+# lookup's status bits.  Descriptor: x_start, z_start, x_step, z_step, nx, nz, first_record,
+# rx_depth; record slots 0..12 the 13 parameters, 13 the ICESOL status byte, 14..15 zero.
+ICETAB_DESC = 8                # AIRICE_ICETAB_DESC
+ICETAB_RECORD = 16             # AIRICE_ICETAB_RECORD
+ICETAB_PARAMS = 13             # AIRICE_ICETAB_PARAMS
+ICETAB_ALIGN = 128             # AIRICE_ICETAB_ALIGN: bytes the image's base is aligned to
+ICETAB_MAX_BUILD = 32          # AIRICE_ICETAB_MAX_BUILD: antennas of one build
+ICETAB_CELL, ICETAB_IDW, ICETAB_BAD_ANTENNA = 1, 2, 4
+ICETAB_MISSING = -1000.0       # what MakeTable stores where a slot holds no ray
 
 EXPORTED_SYMBOLS = (
     "airice_last_error", "airice_version", "airice_atmosphere_load", "airice_atmosphere_parse",
@@ -199,6 +209,9 @@ EXPORTED_SYMBOLS = (
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
     "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host",
     "airice_iceray_launch", "airice_iceray_host", "airice_icesol_launch", "airice_icesol_host",
+    "airice_icetab_grid_init", "airice_icetab_grid", "airice_icetab_layout",
+    "airice_icetab_pack_host", "airice_icetab_work_bytes", "airice_icetab_build_launch",
+    "airice_icetab_build_host", "airice_icetab_lookup_launch", "airice_icetab_lookup_host",
     "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
     "airice_kernel_timing", "airice_kernel_time", "airice_launch_count",
@@ -283,6 +296,15 @@ def lib() -> ctypes.CDLL:
         "airice_iceray_host": ([P, P, P, P, S, P, S, P], I),
         "airice_icesol_launch": ([P, P, P, P, P, S, P, S, S, D, D, P, S, P, P], I),
         "airice_icesol_host": ([P, P, P, P, S, D, D, I, P, S, P], I),
+        "airice_icetab_grid_init": ([D, D, D, P], I),
+        "airice_icetab_grid": ([D, D, D, D, ctypes.c_int32, ctypes.c_int32, D, P], I),
+        "airice_icetab_layout": ([P, S, ctypes.POINTER(S)], I),
+        "airice_icetab_pack_host": ([P, S, P, S, P], I),
+        "airice_icetab_work_bytes": ([P, S, ctypes.POINTER(S)], I),
+        "airice_icetab_build_launch": ([P, P, P, S, D, D, P, S, P], I),
+        "airice_icetab_build_host": ([P, P, P, S, D, D], I),
+        "airice_icetab_lookup_launch": ([P, S, P, P, P, S, P, S, P, P], I),
+        "airice_icetab_lookup_host": ([P, S, P, P, P, S, P, S, P], I),
         "airice_table_to_host": ([P, S, S, P, S, P], I),
         "airice_host_register": ([P, S], I),
         "airice_host_unregister": ([P], I),
@@ -332,6 +354,14 @@ def ptr(a) -> ctypes.c_void_p | None:
     if isinstance(a, int):
         return ctypes.c_void_p(a)
     raise TypeError(f"cannot take a pointer of {type(a)!r}")
+
+
+def aligned_doubles(n: int, align: int = ICETAB_ALIGN) -> np.ndarray:
+    """A zeroed float64 array of n elements whose base is ``align``-byte aligned (a view into a
+    larger buffer, which it keeps alive)."""
+    raw = np.zeros(n * 8 + align, dtype=np.uint8)
+    off = (-raw.ctypes.data) % align
+    return raw[off:off + n * 8].view(np.float64)
 
 
 def default_atmosphere_path() -> str:

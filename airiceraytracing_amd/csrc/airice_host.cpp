@@ -14,6 +14,7 @@
 #include "airice_host.h"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
+#include "airice_icetab.hpp"
 
 namespace airice {
 
@@ -358,6 +359,114 @@ int airice_grid_init(airice_grid* g, double depth_cm, double ice_cm, double heig
   int32_t rows = g->height_steps;
   while (rows > 0 && !(g->start_height - g->height_step * (rows - 1) > 0)) --rows;
   g->table_rows = rows;
+  return AIRICE_OK;
+}
+
+// ---- in-ice interpolation tables: the host-only entries (airice_icetab.hpp) -------------------
+int airice_icetab_grid(double x_start, double z_start, double x_step, double z_step, int32_t nx,
+                       int32_t nz, double rx_depth, double* desc8) {
+  if (desc8 == nullptr) {
+    set_error("icetab grid: null argument (desc8)");
+    return AIRICE_EINVAL;
+  }
+  const double d[icetab::kDesc] = {x_start, z_start, x_step, z_step, (double)nx, (double)nz, 0.0,
+                                   rx_depth};
+  if (const char* bad = icetab::bad_grid(d)) {
+    set_error("icetab grid: %s", bad);
+    return AIRICE_EINVAL;
+  }
+  std::memcpy(desc8, d, sizeof(d));
+  return AIRICE_OK;
+}
+
+int airice_icetab_grid_init(double shower_hit_distance, double shower_depth, double rx_depth,
+                            double* desc8) {
+  // MakeTable (.cc:2617-2636) with IceRayTracing.hh's GridWidthX = 40, GridWidthZ = 20 and
+  // GridStepSizeX_O = GridStepSizeZ_O = 0.1.  GridStopX / GridStopZ are set there and never read:
+  // the lookup takes its stops from the last positions.
+  const double width_x = 40, width_z = 20, step_x = 0.1, step_z = 0.1;
+  const int nx = (int)((width_x / step_x) + 1);
+  const int nz = (int)((width_z / step_z) + 1);
+  double x_start = shower_hit_distance - (width_x / 2);
+  if (shower_hit_distance <= width_x / 2) x_start = 0;
+  double z_start = shower_depth - (width_z / 2);
+  const double z_stop = shower_depth + (width_z / 2);
+  if (std::fabs(shower_depth) <= 10 || z_stop >= 0) z_start = -20;
+  return airice_icetab_grid(x_start, z_start, step_x, step_z, nx, nz, rx_depth, desc8);
+}
+
+int airice_icetab_layout(double* descs, size_t n_ant, size_t* n_doubles) {
+  if (descs == nullptr || n_doubles == nullptr) {
+    set_error("icetab layout: null argument (%s)", descs == nullptr ? "descs" : "n_doubles");
+    return AIRICE_EINVAL;
+  }
+  if (n_ant == 0) {
+    set_error("icetab layout: n_ant = 0");
+    return AIRICE_EINVAL;
+  }
+  size_t record = icetab::header_doubles(n_ant) / icetab::kRecord;
+  for (size_t a = 0; a < n_ant; ++a) {
+    double* d = descs + a * icetab::kDesc;
+    if (const char* bad = icetab::bad_grid(d)) {
+      set_error("icetab layout: antenna %zu: %s", a, bad);
+      return AIRICE_EINVAL;
+    }
+    d[icetab::kFirst] = (double)record;
+    record += (size_t)d[icetab::kNx] * (size_t)d[icetab::kNz];
+  }
+  *n_doubles = record * icetab::kRecord;
+  return AIRICE_OK;
+}
+
+int airice_icetab_pack_host(const double* sol18, size_t ld, const uint8_t* status, size_t n,
+                            double* records) {
+  if (n == 0) return AIRICE_OK;
+  if (sol18 == nullptr || status == nullptr || records == nullptr) {
+    set_error("icetab pack: null argument (%s)",
+              sol18 == nullptr ? "sol18" : status == nullptr ? "status" : "records");
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("icetab pack: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    const double* s = sol18 + i;
+    double* rec = records + i * icetab::kRecord;
+    icetab::pack_record([s, ld](int c) { return s[(size_t)c * ld]; }, status[i],
+                        [rec](int c, double v) { rec[c] = v; });
+  }
+  return AIRICE_OK;
+}
+
+int airice_icetab_lookup_host(const double* h_image, size_t n_ant, const int32_t* ant,
+                              const double* x, const double* z, size_t n, double* out, size_t ld,
+                              uint8_t* status) {
+  if (n == 0) return AIRICE_OK;
+  const char* null_arg = h_image == nullptr ? "image" : x == nullptr ? "x" : z == nullptr ? "z"
+                       : out == nullptr ? "out" : nullptr;
+  if (null_arg != nullptr) {
+    set_error("icetab lookup: null argument (%s)", null_arg);
+    return AIRICE_EINVAL;
+  }
+  if ((reinterpret_cast<uintptr_t>(h_image) & (AIRICE_ICETAB_ALIGN - 1)) != 0) {
+    set_error("icetab lookup: image is not %d-byte aligned", AIRICE_ICETAB_ALIGN);
+    return AIRICE_EINVAL;
+  }
+  if (n_ant == 0) {
+    set_error("icetab lookup: n_ant = 0");
+    return AIRICE_EINVAL;
+  }
+  if (ld < n) {
+    set_error("icetab lookup: ld (%zu) < n (%zu)", ld, n);
+    return AIRICE_EINVAL;
+  }
+  for (size_t i = 0; i < n; ++i) {
+    double* o = out + i;
+    const uint8_t st = icetab::lookup_one(h_image, n_ant, ant != nullptr ? ant[i] : 0, x[i], z[i],
+                                          [o, ld](int c, double v) { o[(size_t)c * ld] = v; });
+    if (status != nullptr) status[i] = st;
+  }
   return AIRICE_OK;
 }
 

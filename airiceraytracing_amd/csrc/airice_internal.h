@@ -208,6 +208,9 @@ enum KTimerId {
   KT_AIR2ICE,
   KT_ICERAY,
   KT_ICESOL,
+  KT_ICETAB_POINTS,
+  KT_ICETAB_PACK,
+  KT_ICETAB_LOOKUP,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -239,6 +242,9 @@ enum LaunchId {
   LC_AIR_PART,      // air_part_kernel (fills a table launch's air record)
   LC_ICERAY,        // iceray_kernel (batched in-ice direct / reflected / refracted solve)
   LC_ICESOL,        // icesol_kernel (the two rays a receiver sees, attenuation, focusing)
+  LC_ICETAB_POINTS, // icetab_points_kernel (an in-ice table build's positions and header)
+  LC_ICETAB_PACK,   // icetab_pack_kernel (one record per position)
+  LC_ICETAB_LOOKUP, // icetab_lookup_kernel (the in-ice table read)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

@@ -5,16 +5,41 @@
 // the same header's pieces; GetRayTracingSolutions and GetFocusingFactor are icesol_host_one (the
 // function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's.  No HIP here, so this file also builds into the sanitizer driver
 // (tests/cpp/iceray_driver.cpp, `make iceray_asan`).
+// The interpolation tables (SetNumberOfAntennas, MakeTable, GetInterpolatedValue and their
+// extensions, at the end) keep one image per antenna in host memory and read it on the calling
+// thread with airice_icetab.hpp; only the builds and the batch read go to the device, through
+// entry points this file references weakly, so that the host-only sanitizer drivers link without
+// them (there MakeTable, MakeTables and GetInterpolatedValuesBatch report AIRICE_EHIP).
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <vector>
 
 #include "IceRayTracing.hh"
 #include "airice_host.h"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
+#include "airice_icetab.hpp"
+
+// The device entries of the tables: null in a program built without the device runtime.
+extern "C" {
+int airice_icetab_build_host(const double *, double *, const double *, size_t, double, double)
+    __attribute__((weak));
+int airice_icetab_lookup_launch(const double *, size_t, const int32_t *, const double *,
+                                const double *, size_t, double *, size_t, uint8_t *, void *)
+    __attribute__((weak));
+int airice_malloc(void **, size_t) __attribute__((weak));
+int airice_free(void *) __attribute__((weak));
+int airice_memcpy_h2d(void *, const void *, size_t) __attribute__((weak));
+int airice_memcpy_d2h(void *, const void *, size_t) __attribute__((weak));
+}
 
 namespace ir = airice::iceray;
 namespace is = airice::icesol;
+namespace it = airice::icetab;
 
 namespace IceRayTracing {
 
@@ -229,6 +254,253 @@ void GetFocusingFactor(double zT, double xR, double zR, double focusing[2]) {
   if (st & AIRICE_ICESOL_FOCUS0) focusing[0] = o[AIRICE_ICESOL_FOCUSING];
   if (st & AIRICE_ICESOL_FOCUS1) focusing[1] = o[AIRICE_ICESOL_FOCUSING + 1];
   if (zR == zT && focusing[0] == 0) focusing[0] = 1.;
+}
+
+// ---- interpolation tables (.cc:2614-2905, 3212-3216) -------------------------------------------
+// One image per antenna (n_ant = 1: a 16-double header, then the records), so MakeTable for one
+// antenna touches no other.  Like the reference's namespace statics this state is not reentrant.
+namespace {
+
+struct FreeDeleter {
+  void operator()(double *p) const { std::free(p); }
+};
+using ImagePtr = std::unique_ptr<double, FreeDeleter>;
+
+ImagePtr alloc_image(size_t doubles) {
+  const size_t bytes = (sizeof(double) * doubles + AIRICE_ICETAB_ALIGN - 1) / AIRICE_ICETAB_ALIGN *
+                       AIRICE_ICETAB_ALIGN;
+  return ImagePtr(static_cast<double *>(std::aligned_alloc(AIRICE_ICETAB_ALIGN, bytes)));
+}
+
+struct AntennaTable {
+  ImagePtr image;
+  size_t doubles = 0;
+};
+std::vector<AntennaTable> g_tables;
+
+// The device copy GetInterpolatedValuesBatch reads: the antennas that have a table, joined into
+// one image; slot[AntNum] is the antenna's index there (-1: no table).
+struct DeviceTables {
+  void *image = nullptr;
+  size_t n_ant = 0;
+  std::vector<int32_t> slot;
+  void drop() {
+    if (image != nullptr && airice_free != nullptr) (void)airice_free(image);
+    image = nullptr;
+    n_ant = 0;
+    slot.clear();
+  }
+  ~DeviceTables() { drop(); }
+} g_device;
+
+const double *table_of(int AntNum) {
+  if (AntNum < 0 || (size_t)AntNum >= g_tables.size()) return nullptr;
+  return g_tables[(size_t)AntNum].image.get();
+}
+
+// A fresh image for AntNum with the descriptor laid out for one antenna; nullptr on failure.
+double *new_table(int AntNum, const double desc8[8]) {
+  if (AntNum < 0) {
+    airice::set_error("IceRayTracing tables: AntNum = %d", AntNum);
+    return nullptr;
+  }
+  double d[it::kDesc];
+  std::copy(desc8, desc8 + it::kDesc, d);
+  size_t doubles = 0;
+  if (airice_icetab_layout(d, 1, &doubles) != AIRICE_OK) return nullptr;
+  ImagePtr image = alloc_image(doubles);
+  if (!image) {
+    airice::set_error("IceRayTracing tables: out of memory (%zu doubles)", doubles);
+    return nullptr;
+  }
+  std::fill(image.get(), image.get() + it::header_doubles(1), 0.0);
+  std::copy(d, d + it::kDesc, image.get());
+  if ((size_t)AntNum >= g_tables.size()) g_tables.resize((size_t)AntNum + 1);
+  g_device.drop();
+  g_tables[(size_t)AntNum].image = std::move(image);
+  g_tables[(size_t)AntNum].doubles = doubles;
+  return g_tables[(size_t)AntNum].image.get();
+}
+
+void drop_table(int AntNum) {
+  if (AntNum >= 0 && (size_t)AntNum < g_tables.size()) g_tables[(size_t)AntNum] = AntennaTable();
+  g_device.drop();
+}
+
+int no_device(const char *who) {
+  airice::set_error("IceRayTracing::%s: this program was built without the device runtime", who);
+  return AIRICE_EHIP;
+}
+
+}  // namespace
+
+void SetNumberOfAntennas(int numberOfAntennas) {
+  g_tables.resize(numberOfAntennas > 0 ? (size_t)numberOfAntennas : 0);
+  g_device.drop();
+}
+
+int MakeTables(double ShowerHitDistance, double ShowerDepth, const double *zR, int n_ant) {
+  if (zR == nullptr || n_ant <= 0) {
+    airice::set_error("IceRayTracing::MakeTables: null zR or n_ant = %d", n_ant);
+    return AIRICE_EINVAL;
+  }
+  if (airice_icetab_build_host == nullptr) return no_device("MakeTables");
+  const double m[3] = {A_ice, B_ice, C_ice};
+  for (int a0 = 0; a0 < n_ant; a0 += AIRICE_ICETAB_MAX_BUILD) {  // one build per 32 antennas
+    const int na = std::min(n_ant - a0, (int)AIRICE_ICETAB_MAX_BUILD);
+    std::vector<double> descs((size_t)na * it::kDesc);
+    for (int a = 0; a < na; a++)
+      if (int rc = airice_icetab_grid_init(ShowerHitDistance, ShowerDepth, zR[a0 + a],
+                                           descs.data() + (size_t)a * it::kDesc))
+        return rc;
+    size_t doubles = 0;
+    if (int rc = airice_icetab_layout(descs.data(), (size_t)na, &doubles)) return rc;
+    ImagePtr joint = alloc_image(doubles);
+    if (!joint) {
+      airice::set_error("IceRayTracing::MakeTables: out of memory (%zu doubles)", doubles);
+      return AIRICE_ENOMEM;
+    }
+    // A0 = 1, frequency = 0.1 GHz (.cc:2652-2653)
+    if (int rc = airice_icetab_build_host(m, joint.get(), descs.data(), (size_t)na, 1, 0.1))
+      return rc;
+    for (int a = 0; a < na; a++) {
+      const double *d = descs.data() + (size_t)a * it::kDesc;
+      double *image = new_table(a0 + a, d);
+      if (image == nullptr) return AIRICE_ENOMEM;
+      const size_t records = (size_t)d[it::kNx] * (size_t)d[it::kNz];
+      std::copy(joint.get() + (size_t)d[it::kFirst] * it::kRecord,
+                joint.get() + ((size_t)d[it::kFirst] + records) * it::kRecord,
+                image + it::header_doubles(1));
+    }
+  }
+  return AIRICE_OK;
+}
+
+// Replaces AntNum's table; prints no "The table took ... ms to make" (IceRayTracing.hh)
+void MakeTable(double ShowerHitDistance, double ShowerDepth, double zR, int AntNum) {
+  int rc = AIRICE_OK;
+  double desc[it::kDesc];
+  double *image = nullptr;
+  if (airice_icetab_build_host == nullptr) rc = no_device("MakeTable");
+  if (rc == AIRICE_OK) rc = airice_icetab_grid_init(ShowerHitDistance, ShowerDepth, zR, desc);
+  if (rc == AIRICE_OK && (image = new_table(AntNum, desc)) == nullptr) rc = AIRICE_EINVAL;
+  if (rc == AIRICE_OK) {
+    const double m[3] = {A_ice, B_ice, C_ice};
+    rc = airice_icetab_build_host(m, image, image, 1, 1, 0.1);
+    if (rc != AIRICE_OK) drop_table(AntNum);
+  }
+  if (rc != AIRICE_OK)
+    std::fprintf(stderr, "IceRayTracing::MakeTable: %s\n", airice_last_error());
+}
+
+int SetTable(int AntNum, const double desc8[8], const double *values13) {
+  if (desc8 == nullptr || values13 == nullptr) {
+    airice::set_error("IceRayTracing::SetTable: null argument");
+    return AIRICE_EINVAL;
+  }
+  double *image = new_table(AntNum, desc8);
+  if (image == nullptr) return AIRICE_EINVAL;
+  const size_t records = (size_t)image[it::kNx] * (size_t)image[it::kNz];
+  double *rec = image + it::header_doubles(1);
+  for (size_t r = 0; r < records; r++, rec += it::kRecord) {
+    for (int c = 0; c < it::kParams; c++) rec[c] = values13[(size_t)c * records + r];
+    for (int c = it::kParams; c < it::kRecord; c++) rec[c] = 0.0;
+  }
+  return AIRICE_OK;
+}
+
+double GetInterpolatedValue(double xT, double zT, int rtParameter, int AntNum) {
+  const double *image = table_of(AntNum);
+  if (image == nullptr || rtParameter < 0 || rtParameter >= it::kParams) return it::kMissing;
+  it::Cell cell;
+  if (!it::find_cell(image, xT, zT, &cell)) return it::kMissing;
+  size_t off[4];
+  it::corner_offsets(cell, off);
+  bool idw = false;
+  return it::interpolate(cell, image[off[0] + rtParameter], image[off[1] + rtParameter],
+                         image[off[2] + rtParameter], image[off[3] + rtParameter], &idw);
+}
+
+void GetInterpolatedValues(double xT, double zT, int AntNum, double out[13]) {
+  const double *image = table_of(AntNum);
+  if (image == nullptr) {
+    std::fill(out, out + it::kParams, it::kMissing);
+    return;
+  }
+  it::lookup_one(image, 1, 0, xT, zT, [out](int c, double v) { out[c] = v; });
+}
+
+int GetInterpolatedValuesBatch(const int *AntNum, const double *xT, const double *zT, size_t n,
+                               double *out, size_t ld, uint8_t *status) {
+  if (n == 0) return AIRICE_OK;
+  if (xT == nullptr || zT == nullptr || out == nullptr || ld < n) {
+    airice::set_error("IceRayTracing::GetInterpolatedValuesBatch: null argument or ld < n");
+    return AIRICE_EINVAL;
+  }
+  if (airice_icetab_lookup_launch == nullptr || airice_malloc == nullptr)
+    return no_device("GetInterpolatedValuesBatch");
+  if (g_device.image == nullptr) {  // join the antennas that have a table and upload them
+    std::vector<double> descs;
+    std::vector<int32_t> slot(g_tables.size(), -1);
+    for (size_t a = 0; a < g_tables.size(); a++)
+      if (g_tables[a].image) {
+        slot[a] = (int32_t)(descs.size() / it::kDesc);
+        descs.insert(descs.end(), g_tables[a].image.get(), g_tables[a].image.get() + it::kDesc);
+      }
+    const size_t n_ant = descs.size() / it::kDesc;
+    if (n_ant == 0) {
+      airice::set_error("IceRayTracing::GetInterpolatedValuesBatch: no antenna has a table");
+      return AIRICE_EINVAL;
+    }
+    size_t doubles = 0;
+    if (int rc = airice_icetab_layout(descs.data(), n_ant, &doubles)) return rc;
+    std::vector<double> joint(doubles, 0.0);
+    std::copy(descs.begin(), descs.end(), joint.begin());
+    for (size_t a = 0; a < g_tables.size(); a++)
+      if (slot[a] >= 0) {
+        const double *d = descs.data() + (size_t)slot[a] * it::kDesc;
+        std::copy(g_tables[a].image.get() + it::header_doubles(1),
+                  g_tables[a].image.get() + g_tables[a].doubles,
+                  joint.begin() + (size_t)d[it::kFirst] * it::kRecord);
+      }
+    void *dev = nullptr;
+    if (int rc = airice_malloc(&dev, sizeof(double) * doubles)) return rc;
+    if (int rc = airice_memcpy_h2d(dev, joint.data(), sizeof(double) * doubles)) {
+      (void)airice_free(dev);
+      return rc;
+    }
+    g_device.image = dev;
+    g_device.n_ant = n_ant;
+    g_device.slot = slot;
+  }
+  // queries: ant (4 n, padded) | x | z | out (13 n) | status
+  std::vector<int32_t> ant(n);
+  for (size_t i = 0; i < n; i++) {
+    const int a = AntNum != nullptr ? AntNum[i] : 0;
+    const bool known = a >= 0 && (size_t)a < g_device.slot.size() && g_device.slot[(size_t)a] >= 0;
+    ant[i] = known ? g_device.slot[(size_t)a] : (int32_t)g_device.n_ant;  // -> BAD_ANTENNA, -1000
+  }
+  const size_t ant_bytes = (sizeof(int32_t) * n + 15) / 16 * 16;
+  const size_t bytes = ant_bytes + sizeof(double) * (2 + it::kParams) * n + n;
+  void *block = nullptr;
+  if (int rc = airice_malloc(&block, bytes)) return rc;
+  char *base = static_cast<char *>(block);
+  double *dx = reinterpret_cast<double *>(base + ant_bytes);
+  double *dz = dx + n, *dout = dz + n;
+  uint8_t *dst = reinterpret_cast<uint8_t *>(dout + (size_t)it::kParams * n);
+  int rc = airice_memcpy_h2d(base, ant.data(), sizeof(int32_t) * n);
+  if (rc == AIRICE_OK) rc = airice_memcpy_h2d(dx, xT, sizeof(double) * n);
+  if (rc == AIRICE_OK) rc = airice_memcpy_h2d(dz, zT, sizeof(double) * n);
+  if (rc == AIRICE_OK)
+    rc = airice_icetab_lookup_launch(static_cast<const double *>(g_device.image), g_device.n_ant,
+                                     reinterpret_cast<const int32_t *>(base), dx, dz, n, dout, n,
+                                     dst, nullptr);
+  // the copies back are on the null stream, like the launch: they wait for the kernel
+  for (int c = 0; c < it::kParams && rc == AIRICE_OK; c++)
+    rc = airice_memcpy_d2h(out + (size_t)c * ld, dout + (size_t)c * n, sizeof(double) * n);
+  if (rc == AIRICE_OK && status != nullptr) rc = airice_memcpy_d2h(status, dst, n);
+  (void)airice_free(block);
+  return rc;
 }
 
 }  // namespace IceRayTracing

@@ -99,6 +99,130 @@ class AntennaTables:
         return out, ok, flags
 
 
+class IceTables:
+    """The in-ice interpolation tables of some antennas (IceRayTracing::MakeTable): one image of
+    float64 on the device -- ``image``, laid out as include/airice.h says -- and its descriptors
+    ``descs`` ((n_ant, 8) numpy: x_start, z_start, x_step, z_step, nx, nz, first_record,
+    rx_depth).  ``lookup`` is IceRayTracing::GetInterpolatedValue for all 13 parameters of many
+    points in one launch."""
+
+    def __init__(self, image, descs):
+        self.image = image
+        self.descs = descs
+        self.n_ant = int(descs.shape[0])
+        self._host = None
+
+    def lookup(self, x, z, ant=None, out=None, status=None, ld: int | None = None, stream=None):
+        """airice_icetab_lookup_launch on device tensors: ``x``, ``z`` (n float64), ``ant`` (n
+        int32, None: antenna 0); parameter c of query i lands at ``out[c, i]`` (13 x ld float64,
+        allocated when None), ``status`` (n uint8, optional) takes the _lib.ICETAB_* bits.
+        Stream-ordered; returns ``out``."""
+        import torch
+        n = int(x.numel())
+        if out is None:
+            out = torch.empty((_lib.ICETAB_PARAMS, n if ld is None else ld), dtype=torch.float64,
+                              device=x.device)
+        check(lib().airice_icetab_lookup_launch(
+            ptr(self.image), self.n_ant, ptr(ant), ptr(x), ptr(z), n, ptr(out),
+            int(out.stride(0)) if ld is None else ld, ptr(status), _stream_handle(stream)),
+            "airice_icetab_lookup_launch")
+        return out
+
+    def host_image(self) -> np.ndarray:
+        """The image in host memory (aligned; copied from the device once and kept)."""
+        if self._host is None:
+            import torch
+            torch.cuda.synchronize(self.image.device)
+            h = _lib.aligned_doubles(int(self.image.numel()))
+            check(lib().airice_memcpy_d2h(ptr(h), ptr(self.image), h.nbytes), "airice_memcpy_d2h")
+            self._host = h
+        return self._host
+
+    def lookup_host(self, x, z, ant=None):
+        """airice_icetab_lookup_host: numpy in, (out (13, n), status (n) uint8) out, on the calling
+        thread against ``host_image()``."""
+        return icetab_lookup_host(self.host_image(), self.n_ant, x, z, ant)
+
+    def values(self, ant: int) -> np.ndarray:
+        """Antenna ``ant``'s table as the reference's 13 columns: a (13, nx, nz) numpy array."""
+        return icetab_values(self.host_image(), self.descs, ant)
+
+
+def icetab_descs(grids) -> tuple[np.ndarray, int]:
+    """(n_ant, 8) descriptors with first_record filled (airice_icetab_layout) and the image's
+    size in doubles."""
+    d = np.array(grids, dtype=np.float64).reshape(-1, _lib.ICETAB_DESC)
+    d = np.ascontiguousarray(d)
+    size = ctypes.c_size_t(0)
+    check(lib().airice_icetab_layout(ptr(d), d.shape[0], ctypes.byref(size)),
+          "airice_icetab_layout")
+    return d, int(size.value)
+
+
+def icetab_grid(x_start, z_start, x_step, z_step, nx, nz, rx_depth) -> np.ndarray:
+    """airice_icetab_grid: the 8-double descriptor of any grid (first_record 0 until a layout)."""
+    d = np.zeros(_lib.ICETAB_DESC, dtype=np.float64)
+    check(lib().airice_icetab_grid(float(x_start), float(z_start), float(x_step), float(z_step),
+                                   int(nx), int(nz), float(rx_depth), ptr(d)),
+          "airice_icetab_grid")
+    return d
+
+
+def icetab_grid_init(shower_hit_distance, shower_depth, rx_depth) -> np.ndarray:
+    """airice_icetab_grid_init: MakeTable's own 401 x 201 grid around the shower."""
+    d = np.zeros(_lib.ICETAB_DESC, dtype=np.float64)
+    check(lib().airice_icetab_grid_init(float(shower_hit_distance), float(shower_depth),
+                                        float(rx_depth), ptr(d)), "airice_icetab_grid_init")
+    return d
+
+
+def icetab_image_from_values(descs, values) -> tuple[np.ndarray, np.ndarray]:
+    """The host image (aligned) of tables given as the reference's columns: ``values[a]`` is
+    (13, nx, nz).  Slots 13..15 of every record are 0.  Returns (image, descs with layout)."""
+    d, size = icetab_descs(descs)
+    image = _lib.aligned_doubles(size)
+    image[:d.size] = d.ravel()
+    for a in range(d.shape[0]):
+        nx, nz, first = int(d[a, 4]), int(d[a, 5]), int(d[a, 6])
+        v = np.asarray(values[a], dtype=np.float64).reshape(_lib.ICETAB_PARAMS, nx * nz)
+        rec = image[first * _lib.ICETAB_RECORD:(first + nx * nz) * _lib.ICETAB_RECORD]
+        rec.reshape(nx * nz, _lib.ICETAB_RECORD)[:, :_lib.ICETAB_PARAMS] = v.T
+    return image, d
+
+
+def icetab_values(image, descs, ant: int) -> np.ndarray:
+    nx, nz, first = int(descs[ant, 4]), int(descs[ant, 5]), int(descs[ant, 6])
+    rec = np.asarray(image)[first * _lib.ICETAB_RECORD:(first + nx * nz) * _lib.ICETAB_RECORD]
+    rec = rec.reshape(nx * nz, _lib.ICETAB_RECORD)
+    return np.ascontiguousarray(rec[:, :_lib.ICETAB_PARAMS].T).reshape(_lib.ICETAB_PARAMS, nx, nz)
+
+
+def icetab_lookup_host(image, n_ant: int, x, z, ant=None):
+    """airice_icetab_lookup_host on a host image (128-byte aligned numpy float64)."""
+    arrs = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in (x, z)])
+    xs, zs = [np.ascontiguousarray(v).ravel() for v in arrs]
+    n = xs.size
+    a = None
+    if ant is not None:
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(ant, dtype=np.int32), xs.shape))
+    out = np.empty((_lib.ICETAB_PARAMS, n), dtype=np.float64)
+    st = np.empty(n, dtype=np.uint8)
+    check(lib().airice_icetab_lookup_host(ptr(image), n_ant, ptr(a), ptr(xs), ptr(zs), n, ptr(out),
+                                          max(n, 1), ptr(st)), "airice_icetab_lookup_host")
+    return out, st
+
+
+def icetab_pack_host(sol, status) -> np.ndarray:
+    """airice_icetab_pack_host: (18, n) solution columns and n status bytes -> (n, 16) records."""
+    sol = np.ascontiguousarray(sol, dtype=np.float64)
+    status = np.ascontiguousarray(status, dtype=np.uint8)
+    n = sol.shape[1]
+    rec = np.empty((n, _lib.ICETAB_RECORD), dtype=np.float64)
+    check(lib().airice_icetab_pack_host(ptr(sol), max(n, 1), ptr(status), n, ptr(rec)),
+          "airice_icetab_pack_host")
+    return rec
+
+
 class AirIceSolver:
     """One medium (parsed GDAS atmosphere + ice model) and the batched GPU entry points."""
 
@@ -559,6 +683,51 @@ class AirIceSolver:
                                        float(frequency), 1 if focusing else 0, ptr(out),
                                        max(n, 1), ptr(st)), "airice_icesol_host")
         return out, st
+
+    # ------------------------------------------------------------------ in-ice tables
+    def ice_tables(self, shower_hit_distance, shower_depth, rx_depths, a0: float = 1.0,
+                   frequency: float = 0.1, model=None, grids=None, stream=None) -> IceTables:
+        """airice_icetab_build_launch: IceRayTracing::MakeTable for the antennas at depths
+        ``rx_depths`` (at most _lib.ICETAB_MAX_BUILD) in four launches -- the grid positions, the
+        in-ice solver over every position and its receiver 1 cm lower, the two-ray solutions with
+        attenuation and focusing, and the pack into records.  The grid is MakeTable's 401 x 201
+        around (``shower_hit_distance``, ``shower_depth``), or ``grids``: one descriptor per
+        antenna (``icetab_grid``).  ``a0`` and ``frequency`` (GHz) default to MakeTable's 1 and
+        0.1.  Stream-ordered; the work buffer is freed once the stream has used it."""
+        import torch
+        if grids is None:
+            grids = [icetab_grid_init(shower_hit_distance, shower_depth, zr)
+                     for zr in np.atleast_1d(np.asarray(rx_depths, dtype=np.float64))]
+        descs, size = icetab_descs(grids)
+        n_ant = descs.shape[0]
+        work = ctypes.c_size_t(0)
+        check(lib().airice_icetab_work_bytes(ptr(descs), n_ant, ctypes.byref(work)),
+              "airice_icetab_work_bytes")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        image = torch.empty(size, dtype=torch.float64, device=dev)
+        buf = torch.empty((work.value + 7) // 8, dtype=torch.float64, device=dev)
+        m = self._ice_model(model)
+        check(lib().airice_icetab_build_launch(ptr(m), ptr(image), ptr(descs), n_ant, float(a0),
+                                               float(frequency), ptr(buf), buf.numel() * 8,
+                                               _stream_handle(stream)),
+              "airice_icetab_build_launch")
+        if isinstance(stream, torch.cuda.Stream):
+            buf.record_stream(stream)
+            image.record_stream(stream)
+        return IceTables(image, descs)
+
+    def ice_tables_from_values(self, descs, values) -> IceTables:
+        """An ``IceTables`` from tables in the reference's column form (saved tables, tests):
+        ``descs`` one descriptor per antenna, ``values[a]`` (13, nx, nz).  The image is assembled
+        on the host and uploaded with airice_memcpy_h2d."""
+        import torch
+        image, d = icetab_image_from_values(descs, values)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dimage = torch.empty(image.size, dtype=torch.float64, device=dev)
+        check(lib().airice_memcpy_h2d(ptr(dimage), ptr(image), image.nbytes), "airice_memcpy_h2d")
+        t = IceTables(dimage, d)
+        t._host = image
+        return t
 
     # ------------------------------------------------------------------ pythonwrapper
     def trace_ice_to_air_device(self, depth, ice, txh, dist, out10, stream=None) -> None:

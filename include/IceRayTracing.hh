@@ -29,8 +29,18 @@
  *     n = L, or L >= A, gives NaN; GetIceTemperature is the cubic in Horner form.  It needs
  *     B < 0 < C.  A NaN or infinite input of GetRayTracingSolutions gives NaN values with
  *     IgnoreCh 0.
- * Not provided: the _Cnz and _Air variants, DirectRayTracer, MakeTable and its
- * interpolation, the GetFull*RayPath samplers, and FindFunctionRoot* with GSL-typed arguments.
+ *   - SetNumberOfAntennas, MakeTable and GetInterpolatedValue are the reference's three-call table
+ *     workflow.  MakeTable solves its 401 x 201 grid on the GPU in four launches and
+ *     keeps the table in host memory; GetInterpolatedValue runs on the calling thread (bit for bit
+ *     airice_icetab_lookup_host).  Differences: MakeTable does not print "The table took ... ms to
+ *     make"; a second MakeTable for the same AntNum replaces the table (the reference appends to
+ *     it and then reads the old entries); an rtParameter outside 0..12, or an AntNum without a
+ *     table, returns -1000 (the reference reads out of bounds); grid positions are kept as
+ *     doubles (the reference narrows GridPositionXb / GridPositionZb to float).  MakeTables,
+ *     GetInterpolatedValues, GetInterpolatedValuesBatch and SetTable are extensions.  The table
+ *     state is shared and, like the reference's, not reentrant.
+ * Not provided: the _Cnz and _Air variants, DirectRayTracer, the GetFull*RayPath samplers, and
+ * FindFunctionRoot* with GSL-typed arguments.
  * Link: -L<repo>/airiceraytracing_amd -lairice. */
 #ifndef AIRICE_ICERAYTRACING_HH_
 #define AIRICE_ICERAYTRACING_HH_
@@ -104,6 +114,29 @@ void GetRayTracingSolutions(double RxDepth, double Distance, double TxDepth, dou
                             int IgnoreCh[2], double IncidenceAngleInIce[2], double A0,
                             double frequency, double AttRay[2]);
 void GetFocusingFactor(double zT, double xR, double zR, double focusing[2]);
+
+/* The interpolation tables (.cc:2614-2905, 3212-3216): one table of 13 parameters per antenna over
+ * a 40 m x 20 m grid of transmitter positions around the shower, and its bilinear read (inverse
+ * squared distance over the valid corners where a corner holds -1000).  rtParameter: 0-5 time,
+ * path, launch angle, receive angle, attenuation, focusing of the first ray, 6-11 the same of the
+ * second, 12 the incidence angle in ice. */
+void SetNumberOfAntennas(int numberOfAntennas);
+void MakeTable(double ShowerHitDistance, double ShowerDepth, double zR, int AntNum);
+double GetInterpolatedValue(double xT, double zT, int rtParameter, int AntNum);
+
+/* Extensions.  MakeTables: the tables of antennas 0..n_ant-1 at depths zR[] in one build (four
+ * launches per 32 antennas).  GetInterpolatedValues: all 13 parameters of one point, on the
+ * calling thread.  GetInterpolatedValuesBatch: n points in one launch of icetab_lookup_kernel,
+ * parameter c of point i at out[c*ld + i], status (nullable) the AIRICE_ICETAB_* bits; AntNum NULL
+ * reads antenna 0; the device copy of the tables is kept until the next MakeTable, MakeTables,
+ * SetTable or SetNumberOfAntennas.  SetTable: installs a caller's table -- desc8 as
+ * airice_icetab_grid leaves it, values13[c*nx*nz + ix*nz + iz] the reference's 13 columns.
+ * The int-returning ones give AIRICE_OK or an AIRICE_E* code (airice_last_error()). */
+int MakeTables(double ShowerHitDistance, double ShowerDepth, const double *zR, int n_ant);
+void GetInterpolatedValues(double xT, double zT, int AntNum, double out[13]);
+int GetInterpolatedValuesBatch(const int *AntNum, const double *xT, const double *zT, size_t n,
+                               double *out, size_t ld, uint8_t *status);
+int SetTable(int AntNum, const double desc8[8], const double *values13);
 
 /* n (Tx depth, distance, Rx depth) triples in one kernel launch, with the model SetA / SetB / SetC
  * left: value c of pair i at out[c*ld + i] (AIRICE_ICERAY_FIELDS columns: the 29 of IceRayTracing,

@@ -558,6 +558,84 @@ int airice_icesol_host(const double *model3, const double *z0, const double *x1,
                        size_t n, double a0, double frequency_ghz, int focusing, double *out,
                        size_t ld, uint8_t *status);
 
+/* --- in-ice interpolation tables ---------------------------------------------------------------
+ * IceRayTracing::MakeTable (IceRayTracing.cc:2614-2724) and GetInterpolatedValue (.cc:2727-2905):
+ * per antenna a grid of transmitter positions (xT, zT), 13 numbers per position, and the bilinear
+ * / inverse-distance read of it.  DESIGN.md §10 has the rules as tables.
+ * The image of n_ant antennas' tables is ONE contiguous array of doubles, the same bytes on host
+ * and device, whose base is AIRICE_ICETAB_ALIGN-byte aligned:
+ *   header  n_ant descriptors of AIRICE_ICETAB_DESC doubles {x_start, z_start, x_step, z_step, nx,
+ *           nz, first_record, rx_depth} (counts as exact doubles), zero-padded to a multiple of
+ *           AIRICE_ICETAB_RECORD doubles;
+ *   records AIRICE_ICETAB_RECORD doubles (128 B, one cache line) per grid position; record r is
+ *           at image + 16 r, antenna a's position (ix, iz) is record first_record[a] + ix*nz + iz
+ *           (the reference's ix*TotalStepsZ_O + iz), antenna 0's first record follows the header
+ *           and each antenna's records follow the one before.  Slots 0..12
+ *           (AIRICE_ICETAB_PARAMS) are GridZValueb[AntNum][0..12]: 0-5 time, path, launch angle,
+ *           receive angle, attenuation, focusing of slot 0; 6-11 the same of slot 1; 12 the
+ *           incidence angle in ice; -1000 where MakeTable stores -1000.  Slot 13 is the position's
+ *           AIRICE_ICESOL_* status byte as a double, slots 14 and 15 are 0.0.
+ * A grid position is x_start + x_step*ix, z_start + z_step*iz: a product, then a sum, each rounded,
+ * everywhere (the bits of GridPositionXb / GridPositionZb).
+ * Every argument check below returns AIRICE_EINVAL before any device call, and
+ * airice_last_error() names the argument. */
+#define AIRICE_ICETAB_DESC 8
+#define AIRICE_ICETAB_RECORD 16
+#define AIRICE_ICETAB_PARAMS 13
+#define AIRICE_ICETAB_ALIGN 128
+#define AIRICE_ICETAB_MAX_BUILD 32 /* antennas of one build (their descriptors are a kernel argument) */
+#define AIRICE_ICETAB_CELL 1        /* lookup status: a cell was used */
+#define AIRICE_ICETAB_IDW 2         /* at least one parameter took the inverse-distance branch */
+#define AIRICE_ICETAB_BAD_ANTENNA 4 /* the antenna index is outside [0, n_ant) */
+/* Host: MakeTable's grid (.cc:2617-2636) with the reference's widths (40 m, 20 m) and steps
+ * (0.1 m): nx = 401, nz = 201; x_start = hit - 20, or 0 when hit <= 20; z_start = depth - 10, or
+ * -20 when |depth| <= 10 or depth + 10 >= 0.  first_record is left 0 (airice_icetab_layout). */
+int airice_icetab_grid_init(double shower_hit_distance, double shower_depth, double rx_depth,
+                            double *desc8);
+/* Host: any grid; nx < 2, nz < 2 or a step that is not finite and positive is AIRICE_EINVAL. */
+int airice_icetab_grid(double x_start, double z_start, double x_step, double z_step, int32_t nx,
+                       int32_t nz, double rx_depth, double *desc8);
+/* Host: fills first_record of the n_ant descriptors; *n_doubles = the image's size. */
+int airice_icetab_layout(double *descs, size_t n_ant, size_t *n_doubles);
+/* Host: the pack rule (.cc:2664-2715) for n positions: columns sol18[c*ld + i] (the 18
+ * AIRICE_ICESOL_* columns, with focusing) and status[i] in, records[16 i .. 16 i + 15] out.
+ * Focusing factor k is column 16+k when AIRICE_ICESOL_FOCUSk is set and the value is not NaN, else
+ * 1.0; a slot whose IgnoreCh is 0 packs as -1000, slot 12 is -1000 when IncidenceAngleInIce[1]
+ * is 100. */
+int airice_icetab_pack_host(const double *sol18, size_t ld, const uint8_t *status, size_t n,
+                            double *records);
+/* Bytes of the work buffer of a build of these descriptors (after airice_icetab_layout). */
+int airice_icetab_work_bytes(const double *descs, size_t n_ant, size_t *bytes);
+/* The build: for all P = sum of nx*nz positions of n_ant <= AIRICE_ICETAB_MAX_BUILD antennas,
+ * exactly four launches -- icetab_points_kernel (the header, and each position's (zT, xT, zR) and
+ * (zT, xT, zR - 0.01) as 2P rows), iceray_kernel over the 2P rows (airice_iceray_launch),
+ * icesol_kernel over P (airice_icesol_launch with the second P rows as d_rays_lower),
+ * icetab_pack_kernel (one record per position, the rule of airice_icetab_pack_host).  descs is on
+ * the HOST, as airice_icetab_layout left it; d_image and d_work are device memory.  Stream-ordered,
+ * no device allocation.  AIRICE_EINVAL: a null pointer, n_ant == 0 or above the limit, a
+ * misaligned image, work_bytes too small, and what airice_icesol_launch rejects (a non-finite a0,
+ * a frequency_ghz that is not finite and positive, a model outside B < 0 < C). */
+int airice_icetab_build_launch(const double *model3, double *d_image, const double *descs,
+                               size_t n_ant, double a0, double frequency_ghz, void *d_work,
+                               size_t work_bytes, void *stream);
+/* The same with the image on the host: allocates, builds, copies back, synchronises. */
+int airice_icetab_build_host(const double *model3, double *h_image, const double *descs,
+                             size_t n_ant, double a0, double frequency_ghz);
+/* The lookup: ONE launch of icetab_lookup_kernel, one query per lane; query i reads antenna
+ * d_ant[i] (int32; d_ant NULL: antenna 0) at (d_x[i], d_z[i]) and all 13 parameters land at
+ * d_out[c*ld + i], c < 13 -- what 13 calls of GetInterpolatedValue return (.cc:2736-2816 statement
+ * by statement).  A query outside the grid or on an upper stop, a NaN query and an antenna index
+ * outside [0, n_ant) give -1000 thirteen times.  d_status (nullable): the AIRICE_ICETAB_* bits.
+ * Stream-ordered, no device allocation; n == 0 is AIRICE_OK and launches nothing. */
+int airice_icetab_lookup_launch(const double *d_image, size_t n_ant, const int32_t *d_ant,
+                                const double *d_x, const double *d_z, size_t n, double *d_out,
+                                size_t ld, uint8_t *d_status, void *stream);
+/* The same function on the calling thread for any n, image and arrays in host memory; launches
+ * nothing (the engine of the drop-in's GetInterpolatedValue). */
+int airice_icetab_lookup_host(const double *h_image, size_t n_ant, const int32_t *ant,
+                              const double *x, const double *z, size_t n, double *out, size_t ld,
+                              uint8_t *status);
+
 /* Device bookkeeping (thin wrappers so ctypes callers need no HIP runtime binding). */
 int airice_device_count(int *count);
 int airice_set_device(int device);
@@ -611,7 +689,9 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * hdtip_out / trace_out), "lookup_kernel", "lookup_multi_kernel"
  * (airice_table_lookup_launch_multi), "ray_consts_kernel" and "ray_paths_kernel" (the two
  * kernels of airice_ray_paths_launch), "air2ice_kernel" (airice_air2ice_launch), "iceray_kernel"
- * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch).
+ * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
+ * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
+ * (airice_icetab_lookup_launch).
  * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -627,7 +707,9 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * (airice_table_lookup_launch_multi; it does not count as "lookup_kernel"), "air2ice_kernel"
  * (airice_air2ice_launch; it does not count as "rtf_kernel"), "air_part_kernel" (the fill of a
  * table launch's air record, below; it does not count as "table_kernel"), "iceray_kernel"
- * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch).
+ * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
+ * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
+ * (airice_icetab_lookup_launch).
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
