@@ -45,13 +45,10 @@ int launch_iceray(const double model[3], const double* z0, const double* x1, con
                   size_t n, double* out, size_t ld, uint8_t* status, hipStream_t st) {
   const iceray::IceModel m = {model[0], model[1], model[2]};
   const size_t blocks = (n + kIceRayBlock - 1) / kIceRayBlock;
-  count_launch(LC_ICERAY);
-  ktimer_begin(KT_ICERAY, st);
-  hipLaunchKernelGGL(iceray_kernel, dim3((unsigned)blocks), dim3(kIceRayBlock), 0, st, m, z0, x1,
-                     z1, n, out, ld, status);
-  const hipError_t e = hipGetLastError();
-  ktimer_end(KT_ICERAY, st);
-  return e == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+  return bracket_launch(LC_ICERAY, KT_ICERAY, st, [&] {
+    hipLaunchKernelGGL(iceray_kernel, dim3((unsigned)blocks), dim3(kIceRayBlock), 0, st, m, z0, x1,
+                       z1, n, out, ld, status);
+  });
 }
 
 }  // namespace airice

@@ -60,13 +60,10 @@ int launch_icesol(const double model[3], double a0, double frequency_ghz, const 
   const iceray::IceModel m = {model[0], model[1], model[2]};
   const icesol::Medium q = icesol::make_medium(a0, frequency_ghz);  // uniform over the batch
   const size_t blocks = (n + kIceSolBlock - 1) / kIceSolBlock;
-  count_launch(LC_ICESOL);
-  ktimer_begin(KT_ICESOL, st);
-  hipLaunchKernelGGL(icesol_kernel, dim3((unsigned)blocks), dim3(kIceSolBlock), 0, st, m, q, z0,
-                     x1, z1, rays, ld_rays, rays_lower, ld_lower, n, out, ld, status);
-  const hipError_t e = hipGetLastError();
-  ktimer_end(KT_ICESOL, st);
-  return e == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+  return bracket_launch(LC_ICESOL, KT_ICESOL, st, [&] {
+    hipLaunchKernelGGL(icesol_kernel, dim3((unsigned)blocks), dim3(kIceSolBlock), 0, st, m, q, z0,
+                       x1, z1, rays, ld_rays, rays_lower, ld_lower, n, out, ld, status);
+  });
 }
 
 }  // namespace airice

@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "airice.h"
+#include "airice_hostcall.hpp"
 #include "airice_icetab.hpp"
 #include "airice_internal.h"
 
@@ -123,22 +124,17 @@ __global__ __launch_bounds__(kIceTabBlock) void icetab_lookup_kernel(
   if (status != nullptr) status[i] = (uint8_t)(icetab::kCell | (idw ? icetab::kIdw : 0));
 }
 
-struct DevBlock {
-  void* p = nullptr;
-  ~DevBlock() {
-    if (p != nullptr) (void)hipFree(p);
-  }
-};
-
 bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+int misaligned_image(const char* who, const void* image) {
+  if (!misaligned(image, AIRICE_ICETAB_ALIGN)) return AIRICE_OK;
+  set_error("%s: image is not %d-byte aligned", who, AIRICE_ICETAB_ALIGN);
+  return AIRICE_EINVAL;
+}
 
 // The checks a build shares with the sizing of its work buffer: the descriptors' grids and their
 // first_record fields (as airice_icetab_layout leaves them); *positions = P.
 int check_descs(const char* who, const double* descs, size_t n_ant, size_t* positions) {
-  if (descs == nullptr) {
-    set_error("%s: null argument (descs)", who);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument(who, {{"descs", descs}})) return rc;
   if (n_ant == 0 || n_ant > (size_t)kIceTabMaxBuild) {
     set_error("%s: n_ant = %zu is outside 1..%d", who, n_ant, kIceTabMaxBuild);
     return AIRICE_EINVAL;
@@ -165,12 +161,22 @@ int check_descs(const char* who, const double* descs, size_t n_ant, size_t* posi
   return AIRICE_OK;
 }
 
+// What a build checks of its image and values, on either route; *positions = P.
+int check_build(const void* image, const double* model, const double* descs, size_t n_ant,
+                double a0, double frequency_ghz, size_t* positions) {
+  if (int rc = check_descs("icetab build", descs, n_ant, positions)) return rc;
+  if (int rc = misaligned_image("icetab build", image)) return rc;
+  if (const char* bad = icesol_bad_value(model, a0, frequency_ghz)) {
+    set_error("icetab build: %s", bad);
+    return AIRICE_EINVAL;
+  }
+  return AIRICE_OK;
+}
+
 // in (6 P) | rays (32 x 2 P) | solutions (18 x P) | status (P bytes)
 size_t work_bytes_for(size_t P) {
   return sizeof(double) * (6 + 2 * AIRICE_ICERAY_FIELDS + AIRICE_ICESOL_FIELDS) * P + P;
 }
-
-const double kDefaultModel[3] = {1.78, -0.43, 0.0132};  // IceRayTracing.hh:52-54
 
 }  // namespace
 
@@ -181,10 +187,7 @@ using namespace airice;
 extern "C" {
 
 int airice_icetab_work_bytes(const double* descs, size_t n_ant, size_t* bytes) {
-  if (bytes == nullptr) {
-    set_error("icetab work: null argument (bytes)");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("icetab work", {{"bytes", bytes}})) return rc;
   size_t P = 0;
   if (int rc = check_descs("icetab work", descs, n_ant, &P)) return rc;
   *bytes = work_bytes_for(P);
@@ -194,27 +197,16 @@ int airice_icetab_work_bytes(const double* descs, size_t n_ant, size_t* bytes) {
 int airice_icetab_build_launch(const double* model3, double* d_image, const double* descs,
                                size_t n_ant, double a0, double frequency_ghz, void* d_work,
                                size_t work_bytes, void* stream) {
-  if (d_image == nullptr || d_work == nullptr) {
-    set_error("icetab build: null argument (%s)", d_image == nullptr ? "image" : "work");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("icetab build", {{"image", d_image}, {"work", d_work}})) return rc;
+  const double* model = ice_model_or_default(model3);
   size_t P = 0;
-  if (int rc = check_descs("icetab build", descs, n_ant, &P)) return rc;
-  if (misaligned(d_image, AIRICE_ICETAB_ALIGN)) {
-    set_error("icetab build: image is not %d-byte aligned", AIRICE_ICETAB_ALIGN);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = check_build(d_image, model, descs, n_ant, a0, frequency_ghz, &P)) return rc;
   if (misaligned(d_work, 16)) {
     set_error("icetab build: work is not 16-byte aligned");
     return AIRICE_EINVAL;
   }
   if (work_bytes < work_bytes_for(P)) {
     set_error("icetab build: work_bytes (%zu) < %zu", work_bytes, work_bytes_for(P));
-    return AIRICE_EINVAL;
-  }
-  const double* model = model3 != nullptr ? model3 : kDefaultModel;
-  if (const char* bad = icesol_bad_value(model, a0, frequency_ghz)) {
-    set_error("icetab build: %s", bad);
     return AIRICE_EINVAL;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -233,69 +225,38 @@ int airice_icetab_build_launch(const double* model3, double* d_image, const doub
   uint8_t* status = reinterpret_cast<uint8_t*>(sol + (size_t)AIRICE_ICESOL_FIELDS * P);
   const size_t threads = P > header ? P : header;
   const unsigned blocks = (unsigned)((threads + kIceTabBlock - 1) / kIceTabBlock);
-  count_launch(LC_ICETAB_POINTS);
-  ktimer_begin(KT_ICETAB_POINTS, st);
-  hipLaunchKernelGGL(icetab_points_kernel, dim3(blocks), dim3(kIceTabBlock), 0, st, map, d_image,
-                     header, in, P);
-  hipError_t e = hipGetLastError();
-  ktimer_end(KT_ICETAB_POINTS, st);
-  if (e != hipSuccess) {
-    set_error("icetab points launch failed: %s", hipGetErrorString(e));
-    return AIRICE_EHIP;
-  }
-  int rc = airice_iceray_launch(model, in, in + 2 * P, in + 4 * P, 2 * P, rays, 2 * P, nullptr, st);
+  int rc = bracket_launch(LC_ICETAB_POINTS, KT_ICETAB_POINTS, st, [&] {
+    hipLaunchKernelGGL(icetab_points_kernel, dim3(blocks), dim3(kIceTabBlock), 0, st, map, d_image,
+                       header, in, P);
+  });
+  if (rc) return rc;
+  rc = airice_iceray_launch(model, in, in + 2 * P, in + 4 * P, 2 * P, rays, 2 * P, nullptr, st);
   if (rc) return rc;
   rc = airice_icesol_launch(model, in, in + 2 * P, in + 4 * P, rays, 2 * P, rays + P, 2 * P, P, a0,
                             frequency_ghz, sol, P, status, st);
   if (rc) return rc;
-  count_launch(LC_ICETAB_PACK);
-  ktimer_begin(KT_ICETAB_PACK, st);
-  hipLaunchKernelGGL(icetab_pack_kernel, dim3((unsigned)((P + kIceTabBlock - 1) / kIceTabBlock)),
-                     dim3(kIceTabBlock), 0, st, sol, status, P, d_image + header);
-  e = hipGetLastError();
-  ktimer_end(KT_ICETAB_PACK, st);
-  if (e != hipSuccess) {
-    set_error("icetab pack launch failed: %s", hipGetErrorString(e));
-    return AIRICE_EHIP;
-  }
-  return AIRICE_OK;
+  return bracket_launch(LC_ICETAB_PACK, KT_ICETAB_PACK, st, [&] {
+    hipLaunchKernelGGL(icetab_pack_kernel, dim3((unsigned)((P + kIceTabBlock - 1) / kIceTabBlock)),
+                       dim3(kIceTabBlock), 0, st, sol, status, P, d_image + header);
+  });
 }
 
 int airice_icetab_build_host(const double* model3, double* h_image, const double* descs,
                              size_t n_ant, double a0, double frequency_ghz) {
-  if (h_image == nullptr) {
-    set_error("icetab build: null argument (image)");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("icetab build", {{"image", h_image}})) return rc;
+  const double* model = ice_model_or_default(model3);
   size_t P = 0;
-  if (int rc = check_descs("icetab build", descs, n_ant, &P)) return rc;
-  if (misaligned(h_image, AIRICE_ICETAB_ALIGN)) {
-    set_error("icetab build: image is not %d-byte aligned", AIRICE_ICETAB_ALIGN);
-    return AIRICE_EINVAL;
-  }
-  const double* model = model3 != nullptr ? model3 : kDefaultModel;
-  if (const char* bad = icesol_bad_value(model, a0, frequency_ghz)) {
-    set_error("icetab build: %s", bad);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = check_build(h_image, model, descs, n_ant, a0, frequency_ghz, &P)) return rc;
   const size_t image_bytes = sizeof(double) * (icetab::header_doubles(n_ant) + icetab::kRecord * P);
   const size_t work = work_bytes_for(P);
-  DevBlock dimage, dwork;
-  hipError_t e = hipMalloc(&dimage.p, image_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dwork.p, work);
-  if (e != hipSuccess) {
-    set_error("icetab build: hipMalloc failed: %s", hipGetErrorString(e));
-    return AIRICE_EHIP;
-  }
+  DevBuffer dimage, dwork;
+  HIP_TRY(dimage.alloc(image_bytes));
+  HIP_TRY(dwork.alloc(work));
   const int rc = airice_icetab_build_launch(model, static_cast<double*>(dimage.p), descs, n_ant, a0,
                                             frequency_ghz, dwork.p, work, nullptr);
   if (rc) return rc;
   // the copy-back is on the null stream, like the launches: it waits for the kernels
-  e = hipMemcpy(h_image, dimage.p, image_bytes, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("icetab build: copy back failed: %s", hipGetErrorString(e));
-    return AIRICE_EHIP;
-  }
+  HIP_TRY(hipMemcpy(h_image, dimage.p, image_bytes, hipMemcpyDeviceToHost));
   return AIRICE_OK;
 }
 
@@ -303,41 +264,22 @@ int airice_icetab_lookup_launch(const double* d_image, size_t n_ant, const int32
                                 const double* d_x, const double* d_z, size_t n, double* d_out,
                                 size_t ld, uint8_t* d_status, void* stream) {
   if (n == 0) return AIRICE_OK;
-  const char* null_arg = d_image == nullptr ? "image" : d_x == nullptr ? "x" : d_z == nullptr ? "z"
-                       : d_out == nullptr ? "out" : nullptr;
-  if (null_arg != nullptr) {
-    set_error("icetab lookup: null argument (%s)", null_arg);
-    return AIRICE_EINVAL;
-  }
-  if (misaligned(d_image, AIRICE_ICETAB_ALIGN)) {
-    set_error("icetab lookup: image is not %d-byte aligned", AIRICE_ICETAB_ALIGN);
-    return AIRICE_EINVAL;
-  }
+  const char* who = "icetab lookup";
+  if (int rc = null_argument(who, {{"image", d_image}, {"x", d_x}, {"z", d_z}, {"out", d_out}}))
+    return rc;
+  if (int rc = misaligned_image(who, d_image)) return rc;
   if (n_ant == 0) {
     set_error("icetab lookup: n_ant = 0");
     return AIRICE_EINVAL;
   }
-  if (ld < n) {
-    set_error("icetab lookup: ld (%zu) < n (%zu)", ld, n);
-    return AIRICE_EINVAL;
-  }
-  if (n > (size_t)0x7fffffff * kIceTabBlock) {
-    set_error("icetab lookup: n = %zu exceeds one launch", n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = short_stride(who, "ld", ld, n)) return rc;
+  if (int rc = exceeds_one_launch(who, n, kIceTabBlock)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  count_launch(LC_ICETAB_LOOKUP);
-  ktimer_begin(KT_ICETAB_LOOKUP, st);
-  hipLaunchKernelGGL(icetab_lookup_kernel, dim3((unsigned)((n + kIceTabBlock - 1) / kIceTabBlock)),
-                     dim3(kIceTabBlock), 0, st, d_image, n_ant, d_ant, d_x, d_z, n, d_out, ld,
-                     d_status);
-  const hipError_t e = hipGetLastError();
-  ktimer_end(KT_ICETAB_LOOKUP, st);
-  if (e != hipSuccess) {
-    set_error("icetab lookup launch failed: %s", hipGetErrorString(e));
-    return AIRICE_EHIP;
-  }
-  return AIRICE_OK;
+  return bracket_launch(LC_ICETAB_LOOKUP, KT_ICETAB_LOOKUP, st, [&] {
+    hipLaunchKernelGGL(icetab_lookup_kernel, dim3((unsigned)((n + kIceTabBlock - 1) / kIceTabBlock)),
+                       dim3(kIceTabBlock), 0, st, d_image, n_ant, d_ant, d_x, d_z, n, d_out, ld,
+                       d_status);
+  });
 }
 
 }  // extern "C"

@@ -250,4 +250,20 @@ enum LaunchId {
 extern std::atomic<long long> g_launches[LC_COUNT];
 inline void count_launch(int id) { g_launches[id].fetch_add(1, std::memory_order_relaxed); }
 
+// One kernel launch in its bracket: counted (lc), timed when the bench asks (kt; kNoTimer for a
+// kernel without a timer), and its launch error read before the timer's end event is recorded.
+// launch() issues the one hipLaunchKernelGGL on st.
+constexpr int kNoTimer = -1;
+template <class Launch>
+inline int bracket_launch(int lc, int kt, hipStream_t st, Launch launch) {
+  count_launch(lc);
+  if (kt != kNoTimer) ktimer_begin(kt, st);
+  launch();
+  const hipError_t e = hipGetLastError();
+  if (kt != kNoTimer) ktimer_end(kt, st);
+  if (e == hipSuccess) return AIRICE_OK;
+  set_error("kernel launch failed: %s", hipGetErrorString(e));
+  return AIRICE_EHIP;
+}
+
 }  // namespace airice

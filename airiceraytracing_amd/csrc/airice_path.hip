@@ -355,14 +355,14 @@ int launch_single_ray(const DevMedium& M, const airice_medium* m, double depth, 
     return AIRICE_EINVAL;
   }
   PathConsts* c = reinterpret_cast<PathConsts*>(d_work);  // summary[] first
-  count_launch(LC_SINGLE_RAY);
-  hipLaunchKernelGGL(single_ray_kernel, dim3(1), dim3(64), 0, st, M, P, c);
-  if (d_x != nullptr && d_z != nullptr && n > 0) {
-    const unsigned grid = (unsigned)((n + kPathBlock - 1) / kPathBlock);
-    count_launch(LC_PATH);
+  rc = bracket_launch(LC_SINGLE_RAY, kNoTimer, st, [&] {
+    hipLaunchKernelGGL(single_ray_kernel, dim3(1), dim3(64), 0, st, M, P, c);
+  });
+  if (rc || d_x == nullptr || d_z == nullptr || n <= 0) return rc;
+  const unsigned grid = (unsigned)((n + kPathBlock - 1) / kPathBlock);
+  return bracket_launch(LC_PATH, kNoTimer, st, [&] {
     hipLaunchKernelGGL(path_kernel, dim3(grid), dim3(kPathBlock), 0, st, M, P, c, d_x, d_z);
-  }
-  return hipGetLastError() == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+  });
 }
 
 namespace {
@@ -455,8 +455,10 @@ int launch_ray_paths(const DevMedium& M, const airice_medium* m, double depth, d
   PathTile* d_tiles = reinterpret_cast<PathTile*>(w + rec_bytes);
   PathConsts* d_consts = reinterpret_cast<PathConsts*>(w + rec_bytes + tile_bytes);
   // (a copy from pageable memory returns once the source has been read)
-  if (hipMemcpyAsync(d_recs, recs.data(), rec_bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+  if (hipError_t e = hipMemcpyAsync(d_recs, recs.data(), rec_bytes, hipMemcpyHostToDevice, st)) {
+    set_error("ray paths: record upload failed: %s", hipGetErrorString(e));
     return AIRICE_EHIP;
+  }
   const bool sample = path && total > 0;
   if (sample) {
     std::vector<PathTile> tl;
@@ -465,24 +467,22 @@ int launch_ray_paths(const DevMedium& M, const airice_medium* m, double depth, d
       const long long cnt = offsets[i + 1] - offsets[i];
       for (long long t = 0; t * kPathBlock < cnt; ++t) tl.push_back(PathTile{(int)i, (int)t});
     }
-    if (hipMemcpyAsync(d_tiles, tl.data(), tl.size() * sizeof(PathTile), hipMemcpyHostToDevice,
-                       st) != hipSuccess)
+    if (hipError_t e = hipMemcpyAsync(d_tiles, tl.data(), tl.size() * sizeof(PathTile),
+                                      hipMemcpyHostToDevice, st)) {
+      set_error("ray paths: tile upload failed: %s", hipGetErrorString(e));
       return AIRICE_EHIP;
+    }
   }
   const unsigned cgrid = (unsigned)((n + kConstsBlock - 1) / kConstsBlock);
-  count_launch(LC_RAY_CONSTS);
-  ktimer_begin(KT_RAY_CONSTS, st);
-  hipLaunchKernelGGL(ray_consts_kernel, dim3(cgrid), dim3(kConstsBlock), 0, st, M, d_recs,
-                     d_launch, n, d_consts, d_summary, ld);
-  ktimer_end(KT_RAY_CONSTS, st);
-  if (sample) {
-    count_launch(LC_RAY_PATHS);
-    ktimer_begin(KT_RAY_PATHS, st);
+  const int rc = bracket_launch(LC_RAY_CONSTS, KT_RAY_CONSTS, st, [&] {
+    hipLaunchKernelGGL(ray_consts_kernel, dim3(cgrid), dim3(kConstsBlock), 0, st, M, d_recs,
+                       d_launch, n, d_consts, d_summary, ld);
+  });
+  if (rc || !sample) return rc;
+  return bracket_launch(LC_RAY_PATHS, KT_RAY_PATHS, st, [&] {
     hipLaunchKernelGGL(ray_paths_kernel, dim3((unsigned)tiles), dim3(kPathBlock), 0, st, M, d_recs,
                        d_tiles, d_consts, d_x, d_z);
-    ktimer_end(KT_RAY_PATHS, st);
-  }
-  return hipGetLastError() == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+  });
 }
 
 }  // namespace airice

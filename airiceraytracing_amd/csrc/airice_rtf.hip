@@ -811,13 +811,10 @@ int launch_air2ice(const DevMedium& M, const double* txh, const double* dist, co
                    const double* depth, size_t n, double* out, size_t ld, uint8_t* status,
                    hipStream_t st) {
   const size_t blocks = (n + kAir2IceBlock - 1) / kAir2IceBlock;
-  count_launch(LC_AIR2ICE);
-  ktimer_begin(KT_AIR2ICE, st);
-  hipLaunchKernelGGL(air2ice_kernel, dim3((unsigned)blocks), dim3(kAir2IceBlock), 0, st, M, txh,
-                     dist, ice, depth, n, out, ld, status);
-  const hipError_t e = hipGetLastError();
-  ktimer_end(KT_AIR2ICE, st);
-  return e == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+  return bracket_launch(LC_AIR2ICE, KT_AIR2ICE, st, [&] {
+    hipLaunchKernelGGL(air2ice_kernel, dim3((unsigned)blocks), dim3(kAir2IceBlock), 0, st, M, txh,
+                       dist, ice, depth, n, out, ld, status);
+  });
 }
 
 // One call of any op on one lane (the kernel's lane 0 and the host form, rtf_host): r receives
@@ -925,9 +922,9 @@ int launch_rtf(const DevMedium& M, int op, const double* args, size_t n_args, do
   c.op = op;
   c.n_out = rtf_outputs(op, M.ml);
   for (int i = 0; i < 8; i++) c.a[i] = (size_t)i < n_args ? args[i] : 0.0;
-  count_launch(LC_RTF);
-  hipLaunchKernelGGL(rtf_kernel, dim3(1), dim3(64), 0, st, M, c, d_out, take_scalar_signal());
-  return hipGetLastError() == hipSuccess ? AIRICE_OK : AIRICE_EHIP;
+  return bracket_launch(LC_RTF, kNoTimer, st, [&] {
+    hipLaunchKernelGGL(rtf_kernel, dim3(1), dim3(64), 0, st, M, c, d_out, take_scalar_signal());
+  });
 }
 
 }  // namespace airice

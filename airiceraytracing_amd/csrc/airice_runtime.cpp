@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "airice.h"
+#include "airice_hostcall.hpp"
 #include "airice_internal.h"
 
 namespace airice {
@@ -374,33 +375,8 @@ int ScalarCall::sync() {
 
 // ---- one query of a minimizer entry point -----------------------------------------------------
 // Each *_one below runs its query on the host (the cached folds and the entry point's host route)
-// when scalar_on_host(), else on the device through the scalar slot (slot_call).
-//
-// The slot's layout, the same for every entry point: the query inputs at h[0 .. 3], the outputs
-// (ld = 1) from h[4], the flag bytes at h + 32, past the widest entry point's 17 outputs.
-// n_inline: how many of the inputs also travel in the kernel arguments (ScalarCall::arm).
-// launch(d_in, d_out, d_flag, stream) enqueues the call's one kernel on the device views.
-namespace {
-constexpr int kSlotOut = 4, kSlotFlag = 32;
-template <class Launch>
-int slot_call(const double* in, int n_in, int n_inline, double* out, int n_out, uint8_t* flag,
-              int n_flag, Launch launch) {
-  ScalarCall call;
-  if (!call.ok()) return AIRICE_EHIP;
-  ScalarSlot& s = call.slot();
-  std::copy(in, in + n_in, s.h);
-  uint8_t* flag_h = reinterpret_cast<uint8_t*>(s.h + kSlotFlag);
-  std::copy(flag, flag + n_flag, flag_h);
-  call.arm(s.h, n_inline);
-  int rc = launch(s.d, s.d + kSlotOut, reinterpret_cast<uint8_t*>(s.d + kSlotFlag), s.st);
-  if (rc == AIRICE_OK) rc = call.sync();
-  if (rc) return rc;
-  std::copy(s.h + kSlotOut, s.h + kSlotOut + n_out, out);
-  std::copy(flag_h, flag_h + n_flag, flag);
-  return AIRICE_OK;
-}
-}  // namespace
-
+// when scalar_on_host(), else on the device through the scalar slot (slot_call), as one launch
+// that takes the slot's signal with the query's inputs inline.
 int solve_one(const airice_medium* m, int variant, double ice_h, const double in[4], bool has_thr,
               double* out, uint8_t* status) {
   if (scalar_on_host()) {
@@ -410,11 +386,11 @@ int solve_one(const airice_medium* m, int variant, double ice_h, const double in
     return solve_host_one(*M, *I, variant, in, has_thr, out, status);
   }
   const int fields = variant == AIRICE_VARIANT_PYWRAPPER ? AIRICE_PYSOLVE_FIELDS : AIRICE_SOLVE_FIELDS;
-  return slot_call(in, 4, has_thr ? 4 : 3, out, fields, status, status != nullptr ? 1 : 0,
-                   [&](const double* d, double* o, uint8_t* f, hipStream_t st) {
-                     return airice_solve_launch(m, variant, ice_h, d, d + 1, d + 2,
-                                                has_thr ? d + 3 : nullptr, 1, o, 1,
-                                                status != nullptr ? f : nullptr, st);
+  return slot_call(in, 4, 0, out, fields, status, status != nullptr ? 1 : 0, has_thr ? 4 : 3,
+                   [&](const SlotArgs& s) {
+                     return airice_solve_launch(m, variant, ice_h, s.in, s.in + 1, s.in + 2,
+                                                has_thr ? s.in + 3 : nullptr, 1, s.out, 1,
+                                                status != nullptr ? s.flag : nullptr, s.st);
                    });
 }
 
@@ -426,10 +402,9 @@ int hdtip_one(const airice_medium* m, double ice_cm, const double in[3], double 
     if (int rc = folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I)) return rc;
     return hdtip_host_one(*M, *I, ice_cm, in, out9, ok);
   }
-  return slot_call(in, 3, 3, out9, 9, ok, 1,
-                   [&](const double* d, double* o, uint8_t* f, hipStream_t st) {
-                     return airice_hdtip_launch(m, d, d + 1, d + 2, ice_cm, 1, o, 1, f, st);
-                   });
+  return slot_call(in, 3, 0, out9, 9, ok, 1, 3, [&](const SlotArgs& s) {
+    return airice_hdtip_launch(m, s.in, s.in + 1, s.in + 2, ice_cm, 1, s.out, 1, s.flag, s.st);
+  });
 }
 
 int trace_one(const airice_medium* m, const double in[4], double out10[10]) {
@@ -439,10 +414,9 @@ int trace_one(const airice_medium* m, const double in[4], double out10[10]) {
     if (int rc = folded_ice(m, AIRICE_VARIANT_PYWRAPPER, 0.0, 0.0, &M, &I)) return rc;
     return trace_host_one(*M, *I, in, out10);
   }
-  return slot_call(in, 4, 4, out10, 10, nullptr, 0,
-                   [&](const double* d, double* o, uint8_t*, hipStream_t st) {
-                     return airice_trace_ice_to_air_launch(m, d, d + 1, d + 2, d + 3, 1, o, st);
-                   });
+  return slot_call(in, 4, 0, out10, 10, nullptr, 0, 4, [&](const SlotArgs& s) {
+    return airice_trace_ice_to_air_launch(m, s.in, s.in + 1, s.in + 2, s.in + 3, 1, s.out, s.st);
+  });
 }
 
 int lookup_fallback_one(const airice_medium* m, double src_cm, double dist_cm, double depth_cm,
@@ -456,14 +430,13 @@ int lookup_fallback_one(const airice_medium* m, double src_cm, double dist_cm, d
     if ((rc = folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I))) return rc;
     rc = lookup_fallback_host_one(*M, *I, ice_cm, in, out9, &fb[0], &fb[1]);
   } else {
-    rc = slot_call(in, 3, 0, out9, 9, fb, 2,
-                   [&](const double* d, double* o, uint8_t* f, hipStream_t st) {
-                     DevMedium M;
-                     if (int rm = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M)) return rm;
-                     IceConsts I;
-                     build_ice_consts(M, ice_cm / 100, 0.0, &I);  // as airice_table_lookup_launch
-                     return launch_lookup_fallback(M, I, d, d + 1, d + 2, ice_cm, o, 1, f, f + 1, st);
-                   });
+    rc = slot_call(in, 3, 0, out9, 9, fb, 2, 0, [&](const SlotArgs& s) {
+      DevMedium M;
+      IceConsts I;  // as airice_table_lookup_launch
+      if (int rm = launch_folds(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I)) return rm;
+      return launch_lookup_fallback(M, I, s.in, s.in + 1, s.in + 2, ice_cm, s.out, 1, s.flag,
+                                    s.flag + 1, s.st);
+    });
   }
   if (rc == AIRICE_OK) *ok = fb[0] != 0;
   return rc;
@@ -546,50 +519,21 @@ extern "C" int airice_kernel_time(const char* name, double* total_ms, int64_t* l
   return AIRICE_OK;
 }
 
-namespace {
-// Device buffer freed on every exit path of the *_host entry points.
-struct DevBuffer {
-  void* p = nullptr;
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-  ~DevBuffer() {
-    if (p != nullptr) (void)hipFree(p);
-  }
-};
-}  // namespace
-
-#define HIP_TRY(expr)                                                          \
-  do {                                                                         \
-    hipError_t e_ = (expr);                                                    \
-    if (e_ != hipSuccess) {                                                    \
-      set_error("%s failed: %s", #expr, hipGetErrorString(e_));                \
-      return AIRICE_EHIP;                                                      \
-    }                                                                          \
-  } while (0)
-
 extern "C" {
 
+// The checks and folds of a table call; table: its (required) 11-column table, by name.
 static int table_prepare(const airice_medium* m, const airice_grid* g, int32_t row_begin,
-                         int32_t row_count, size_t ld, DevMedium* M, IceConsts* I) {
+                         int32_t row_count, NamedArg table, size_t ld, DevMedium* M, IceConsts* I) {
   if (g == nullptr || row_begin < 0 || row_count < 0 ||
       (int64_t)row_begin + row_count > g->height_steps) {
     set_error("row range [%d,+%d) outside grid of %d rows", row_begin, row_count,
               g ? g->height_steps : -1);
     return AIRICE_EINVAL;
   }
-  if (ld < (size_t)row_count * (size_t)g->angle_steps) {
-    set_error("ld smaller than the number of rays");
-    return AIRICE_EINVAL;
-  }
-  // The launch constants are a pure function of the medium, the ice height and the antenna depth:
-  // repeated launches (one table per antenna, bench steps) reuse the thread's folds (folded_ice)
-  // instead of re-deriving ~20 host exp()s.
-  const DevMedium* Mc = nullptr;
-  const IceConsts* Ic = nullptr;
-  if (int rc = airice::folded_ice(m, AIRICE_VARIANT_MULTIRAY, g->stop_height, -g->depth_m, &Mc, &Ic))
+  if (int rc = short_stride("table", "ld", ld, (size_t)row_count * (size_t)g->angle_steps))
     return rc;
-  *M = *Mc;
-  *I = *Ic;
-  return AIRICE_OK;
+  if (int rc = null_argument("table", {{"m", m}, table})) return rc;
+  return launch_folds(m, AIRICE_VARIANT_MULTIRAY, g->stop_height, -g->depth_m, M, I);
 }
 
 // rows of [row_begin, row_begin+row_count) the table holds (the reference skips Tx <= 0, .cc:2082)
@@ -602,12 +546,8 @@ int airice_table_launch(const airice_medium* m, const airice_grid* g, int32_t ro
                         void* stream) {
   DevMedium M;
   IceConsts I;
-  int rc = table_prepare(m, g, row_begin, row_count, ld, &M, &I);
+  int rc = table_prepare(m, g, row_begin, row_count, {"d_table", d_table}, ld, &M, &I);
   if (rc) return rc;
-  if (d_table == nullptr) {
-    set_error("null table");
-    return AIRICE_EINVAL;
-  }
   rc = launch_table(M, I, g, row_begin, kept_rows(g, row_begin, row_count), d_table, d_full, ld,
                     (hipStream_t)stream);
   if (rc) set_error("table launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -616,11 +556,14 @@ int airice_table_launch(const airice_medium* m, const airice_grid* g, int32_t ro
 
 int airice_table_launch_multi(const airice_medium* m, const airice_grid* grids, int32_t n_grids,
                               float* const* d_tables, const size_t* lds, void* stream) {
-  if (n_grids < 0 || (n_grids > 0 && (grids == nullptr || d_tables == nullptr || lds == nullptr))) {
-    set_error("null argument");
+  if (n_grids < 0) {
+    set_error("table multi: n_grids = %d", n_grids);
     return AIRICE_EINVAL;
   }
   if (n_grids == 0) return AIRICE_OK;
+  if (int rc = null_argument("table multi", {{"m", m}, {"grids", grids}, {"d_tables", d_tables},
+                                             {"lds", lds}}))
+    return rc;
   DevMedium M;
   int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
   if (rc) return rc;
@@ -643,7 +586,7 @@ int airice_table_host(const airice_medium* m, const airice_grid* g, int32_t row_
                       int32_t row_count, float* h_table, double* h_full, size_t ld) {
   DevMedium M;
   IceConsts I;
-  int rc = table_prepare(m, g, row_begin, row_count, ld, &M, &I);
+  int rc = table_prepare(m, g, row_begin, row_count, {"h_table", h_table}, ld, &M, &I);
   if (rc) return rc;
   DevBuffer dt, df;
   HIP_TRY(dt.alloc(sizeof(float) * 11 * ld));
@@ -665,14 +608,10 @@ int airice_table_host(const airice_medium* m, const airice_grid* g, int32_t row_
 int airice_rays_host(const airice_medium* m, const double* launch_deg, const double* txh,
                      double ice_h_m, double depth_m, int32_t in_ice, size_t n, double* out,
                      size_t ld) {
-  if (m == nullptr || out == nullptr || (n > 0 && (launch_deg == nullptr || txh == nullptr))) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("ld < n");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("rays", {{"m", m}, {"out", out}})) return rc;
+  if (n > 0)
+    if (int rc = null_argument("rays", {{"launch_deg", launch_deg}, {"txh", txh}})) return rc;
+  if (int rc = short_stride("rays", "ld", ld, n)) return rc;
   const DevMedium* M = nullptr;
   const IceConsts* I = nullptr;
   if (int rc = airice::folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_h_m, -depth_m, &M, &I)) return rc;
@@ -685,15 +624,14 @@ int airice_scalar_mode(int mode) { return airice::set_scalar_mode(mode); }
 int airice_rays_launch(const airice_medium* m, const double* d_launch, const double* d_txh,
                        double ice_h_m, double depth_m, int32_t in_ice, size_t n, double* d_out,
                        size_t ld, void* stream) {
+  if (n > 0)
+    if (int rc = null_argument("rays", {{"m", m}, {"d_launch", d_launch}, {"d_txh", d_txh},
+                                        {"d_out", d_out}}))
+      return rc;
+  if (int rc = short_stride("rays", "ld", ld, n)) return rc;
   DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
-  if (rc) return rc;
-  if (ld < n) {
-    set_error("ld < n");
-    return AIRICE_EINVAL;
-  }
   IceConsts I;
-  build_ice_consts(M, ice_h_m, -depth_m, &I);
+  if (int rc = launch_folds(m, AIRICE_VARIANT_MULTIRAY, ice_h_m, -depth_m, &M, &I)) return rc;
   return launch_rays(M, I, d_launch, d_txh, in_ice, n, d_out, ld, (hipStream_t)stream);
 }
 
@@ -701,19 +639,15 @@ int airice_solve_launch(const airice_medium* m, int variant, double ice_h_m, con
                         const double* d_dist, const double* d_depth,
                         const double* d_straight_angle, size_t n, double* d_out, size_t ld,
                         uint8_t* d_status, void* stream) {
-  if (variant != AIRICE_VARIANT_MULTIRAY && variant != AIRICE_VARIANT_PYWRAPPER) {
-    set_error("unknown variant %d", variant);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("ld < n");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = bad_variant("solve", variant)) return rc;
+  if (n > 0)
+    if (int rc = null_argument("solve", {{"m", m}, {"d_txh", d_txh}, {"d_dist", d_dist},
+                                         {"d_depth", d_depth}, {"d_out", d_out}}))
+      return rc;
+  if (int rc = short_stride("solve", "ld", ld, n)) return rc;
   DevMedium M;
-  int rc = build_dev_medium(m, variant, &M);
-  if (rc) return rc;
   IceConsts I;
-  build_ice_consts(M, ice_h_m, 0.0, &I);
+  if (int rc = launch_folds(m, variant, ice_h_m, 0.0, &M, &I)) return rc;
   return launch_solve(M, I, variant, d_txh, d_dist, d_depth, d_straight_angle, n, d_out, ld,
                       d_status, (hipStream_t)stream);
 }
@@ -722,63 +656,40 @@ int airice_solve_host(const airice_medium* m, int variant, double ice_h_m, const
                       const double* dist, const double* depth, const double* straight_angle,
                       size_t n, double* out, size_t ld, uint8_t* status) {
   if (n == 0) return AIRICE_OK;
-  if (ld < n) {
-    set_error("ld < n");
-    return AIRICE_EINVAL;
-  }
-  if (m == nullptr || txh == nullptr || dist == nullptr || depth == nullptr || out == nullptr) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("solve", {{"m", m}, {"txh", txh}, {"dist", dist}, {"depth", depth},
+                                       {"out", out}}))
+    return rc;
+  if (int rc = bad_variant("solve", variant)) return rc;
+  if (int rc = short_stride("solve", "ld", ld, n)) return rc;
   const int fields = variant == AIRICE_VARIANT_PYWRAPPER ? AIRICE_PYSOLVE_FIELDS : AIRICE_SOLVE_FIELDS;
-  if (n == 1 && airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
-    if (variant != AIRICE_VARIANT_MULTIRAY && variant != AIRICE_VARIANT_PYWRAPPER) {
-      set_error("unknown variant %d", variant);
-      return AIRICE_EINVAL;
-    }
-    const double in[4] = {txh[0], dist[0], depth[0],
-                          straight_angle != nullptr ? straight_angle[0] : 0.0};
+  const bool has_thr = straight_angle != nullptr;
+  if (n == 1) {  // one query: where airice_scalar_mode says
+    const double in[4] = {txh[0], dist[0], depth[0], has_thr ? straight_angle[0] : 0.0};
     double o[AIRICE_SOLVE_FIELDS];
     uint8_t st = 0;
-    if (int rc = airice::solve_one(m, variant, ice_h_m, in, straight_angle != nullptr, o, &st))
-      return rc;
-    for (int c = 0; c < fields; ++c) out[(size_t)c * ld] = o[c];
-    if (status) status[0] = st;
+    if (int rc = airice::solve_one(m, variant, ice_h_m, in, has_thr, o, &st)) return rc;
+    scatter_one(o, fields, st, out, ld, status);
     return AIRICE_OK;
   }
-  // one device block: txh | dist | depth | [straight angle] | out (fields x ld) | status
-  const size_t nin = straight_angle != nullptr ? 4 : 3;
-  DevBuffer buf;
-  HIP_TRY(buf.alloc(sizeof(double) * (nin * n + (size_t)fields * ld) + n));
-  double* dt = static_cast<double*>(buf.p);
-  double *dd = dt + n, *dp = dt + 2 * n, *dthr = straight_angle != nullptr ? dt + 3 * n : nullptr;
-  double* dout = dt + nin * n;
-  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)fields * ld);
-  HIP_TRY(hipMemcpy(dt, txh, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dd, dist, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dp, depth, sizeof(double) * n, hipMemcpyHostToDevice));
-  if (dthr != nullptr)
-    HIP_TRY(hipMemcpy(dthr, straight_angle, sizeof(double) * n, hipMemcpyHostToDevice));
-  int rc = airice_solve_launch(m, variant, ice_h_m, dt, dd, dp, dthr, n, dout, ld, dst, nullptr);
-  if (rc == AIRICE_OK) {
-    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * fields * ld, hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
-  }
-  return rc;
+  const double* cols[4] = {txh, dist, depth, straight_angle};
+  return staged_call(cols, has_thr ? 4 : 3, n, 0, fields, out, ld, status, [&](const Staged& s) {
+    return airice_solve_launch(m, variant, ice_h_m, s.col(0), s.col(1), s.col(2),
+                               has_thr ? s.col(3) : nullptr, n, s.out, n, s.status, nullptr);
+  });
 }
 
 int airice_hdtip_launch(const airice_medium* m, const double* d_src_cm, const double* d_dist_cm,
                         const double* d_depth_cm, double ice_cm, size_t n, double* d_out,
                         size_t ld, uint8_t* d_ok, void* stream) {
-  if (ld < n) {
-    set_error("ld < n");
-    return AIRICE_EINVAL;
-  }
+  if (n > 0)
+    if (int rc = null_argument("hdtip", {{"m", m}, {"d_src_cm", d_src_cm}, {"d_dist_cm", d_dist_cm},
+                                         {"d_depth_cm", d_depth_cm}, {"d_out", d_out},
+                                         {"d_ok", d_ok}}))
+      return rc;
+  if (int rc = short_stride("hdtip", "ld", ld, n)) return rc;
   DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
-  if (rc) return rc;
   IceConsts I;
-  build_ice_consts(M, ice_cm / 100, 0.0, &I);
+  if (int rc = launch_folds(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I)) return rc;
   return launch_hdtip(M, I, d_src_cm, d_dist_cm, d_depth_cm, ice_cm, n, d_out, ld, d_ok,
                       (hipStream_t)stream);
 }
@@ -787,31 +698,21 @@ int airice_table_lookup_launch(const airice_medium* m, const airice_lookup_table
                                const double* d_src_cm, const double* d_dist_cm,
                                const double* d_depth_cm, double ice_cm, size_t n, double* d_out,
                                size_t ld, uint8_t* d_ok, uint8_t* d_flags, void* stream) {
-  if (t == nullptr || t->table == nullptr ||
-      (n > 0 && (d_src_cm == nullptr || d_dist_cm == nullptr || d_depth_cm == nullptr ||
-                 d_out == nullptr || d_ok == nullptr || d_flags == nullptr))) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("ld < n");
-    return AIRICE_EINVAL;
-  }
-  if (t->n_entries == 0 || t->ld < t->n_entries || t->total_angle_steps < 1 ||
-      t->total_height_steps < 1 || !(t->height_step > 0) ||
-      (reinterpret_cast<uintptr_t>(t->entries) & 15) != 0) {
-    set_error("invalid lookup table description");
-    return AIRICE_EINVAL;
-  }
+  const char* who = "lookup";
+  if (int rc = null_argument(who, {{"m", m}, {"t", t}})) return rc;
+  if (n > 0)
+    if (int rc = null_argument(who, {{"d_src_cm", d_src_cm}, {"d_dist_cm", d_dist_cm},
+                                     {"d_depth_cm", d_depth_cm}, {"d_out", d_out}, {"d_ok", d_ok},
+                                     {"d_flags", d_flags}}))
+      return rc;
+  if (int rc = short_stride(who, "ld", ld, n)) return rc;
+  if (int rc = bad_lookup_table(who, t)) return rc;
   DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
-  if (rc) return rc;
   IceConsts I;
-  build_ice_consts(M, ice_cm / 100, 0.0, &I);
-  rc = launch_lookup(M, I, t, d_src_cm, d_dist_cm, d_depth_cm, ice_cm, n, d_out, ld, d_ok,
-                     d_flags, (hipStream_t)stream);
-  if (rc) set_error("lookup launch failed: %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  int rc = launch_folds(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I);
+  if (rc) return rc;
+  return launch_lookup(M, I, t, d_src_cm, d_dist_cm, d_depth_cm, ice_cm, n, d_out, ld, d_ok,
+                       d_flags, (hipStream_t)stream);
 }
 
 size_t airice_table_lookup_multi_work_bytes(int32_t n_tables, int32_t n_ant) {
@@ -826,6 +727,7 @@ int airice_table_lookup_launch_multi(const airice_medium* m, const airice_lookup
                                      size_t ld_dist, double ice_cm, size_t n_src, double* d_out,
                                      size_t ld, uint8_t* d_ok, uint8_t* d_flags, void* d_work,
                                      size_t work_bytes, void* stream) {
+  const char* who = "lookup multi";
   if (n_tables < 1 || n_tables > AIRICE_LOOKUP_MAX_TABLES) {
     set_error("lookup multi: n_tables = %d outside 1..%d", n_tables, AIRICE_LOOKUP_MAX_TABLES);
     return AIRICE_EINVAL;
@@ -835,26 +737,18 @@ int airice_table_lookup_launch_multi(const airice_medium* m, const airice_lookup
     return AIRICE_EINVAL;
   }
   const bool work = n_ant > 0 && n_src > 0;
-  if (m == nullptr || tables == nullptr ||
-      (n_ant > 0 && (antenna_table == nullptr || antenna_depth_cm == nullptr)) ||
-      (work && (d_src_cm == nullptr || d_dist_cm == nullptr || d_out == nullptr ||
-                d_ok == nullptr || d_flags == nullptr || d_work == nullptr))) {
-    set_error("lookup multi: null argument");
-    return AIRICE_EINVAL;
-  }
-  for (int32_t i = 0; i < n_tables; ++i) {
-    const airice_lookup_table* t = tables + i;
-    if (t->table == nullptr) {
-      set_error("lookup multi: null argument (tables[%d].table)", i);
-      return AIRICE_EINVAL;
-    }
-    if (t->n_entries == 0 || t->ld < t->n_entries || t->total_angle_steps < 1 ||
-        t->total_height_steps < 1 || !(t->height_step > 0) ||
-        (reinterpret_cast<uintptr_t>(t->entries) & 15) != 0) {
-      set_error("lookup multi: invalid lookup table description (tables[%d])", i);
-      return AIRICE_EINVAL;
-    }
-  }
+  if (int rc = null_argument(who, {{"m", m}, {"tables", tables}})) return rc;
+  if (n_ant > 0)
+    if (int rc = null_argument(who, {{"antenna_table", antenna_table},
+                                     {"antenna_depth_cm", antenna_depth_cm}}))
+      return rc;
+  if (work)
+    if (int rc = null_argument(who, {{"d_src_cm", d_src_cm}, {"d_dist_cm", d_dist_cm},
+                                     {"d_out", d_out}, {"d_ok", d_ok}, {"d_flags", d_flags},
+                                     {"d_work", d_work}}))
+      return rc;
+  for (int32_t i = 0; i < n_tables; ++i)
+    if (int rc = bad_lookup_table(who, tables + i, i)) return rc;
   for (int32_t a = 0; a < n_ant; ++a)
     if (antenna_table[a] < 0 || antenna_table[a] >= n_tables) {
       set_error("lookup multi: antenna_table[%d] = %d outside [0, %d)", a, antenna_table[a],
@@ -881,15 +775,12 @@ int airice_table_lookup_launch_multi(const airice_medium* m, const airice_lookup
     return AIRICE_EINVAL;
   }
   DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
+  IceConsts I;  // as airice_table_lookup_launch
+  int rc = launch_folds(m, AIRICE_VARIANT_MULTIRAY, ice_cm / 100, 0.0, &M, &I);
   if (rc) return rc;
-  IceConsts I;
-  build_ice_consts(M, ice_cm / 100, 0.0, &I);  // as airice_table_lookup_launch
-  rc = launch_lookup_multi(M, I, tables, n_tables, antenna_table, antenna_depth_cm, (size_t)n_ant,
-                           d_src_cm, d_dist_cm, ld_dist, ice_cm, n_src, d_out, ld, d_ok, d_flags,
-                           d_work, (hipStream_t)stream);
-  if (rc) set_error("lookup multi launch failed: %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  return launch_lookup_multi(M, I, tables, n_tables, antenna_table, antenna_depth_cm,
+                             (size_t)n_ant, d_src_cm, d_dist_cm, ld_dist, ice_cm, n_src, d_out, ld,
+                             d_ok, d_flags, d_work, (hipStream_t)stream);
 }
 
 size_t airice_lookup_pack_floats(size_t n_entries, int32_t total_angle_steps) {
@@ -899,10 +790,8 @@ size_t airice_lookup_pack_floats(size_t n_entries, int32_t total_angle_steps) {
 
 int airice_lookup_pack(const airice_lookup_table* t, float* d_entries, size_t capacity_floats,
                        void* stream) {
-  if (t == nullptr || t->table == nullptr || d_entries == nullptr) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("lookup pack", {{"t", t}, {"d_entries", d_entries}})) return rc;
+  if (int rc = null_argument("lookup pack", {{"table", t->table}})) return rc;
   if (t->ld < t->n_entries || (reinterpret_cast<uintptr_t>(d_entries) & 15) != 0) {
     set_error("ld < n_entries or entries not 16-byte aligned");
     return AIRICE_EINVAL;
@@ -925,27 +814,23 @@ int airice_lookup_pack(const airice_lookup_table* t, float* d_entries, size_t ca
 
 int airice_single_ray_plan(const airice_medium* m, double antenna_depth_m, double launch_deg,
                            double txh_m, double ice_m, airice_single_ray_info* info) {
-  if (m == nullptr || info == nullptr) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("single ray", {{"m", m}, {"info", info}})) return rc;
   return plan_single_ray(m, antenna_depth_m, launch_deg, txh_m, ice_m, info);
 }
 
 int airice_single_ray_launch(const airice_medium* m, double antenna_depth_m, double launch_deg,
                              double txh_m, double ice_m, double* d_summary, double* d_x,
                              double* d_z, size_t cap, void* stream) {
-  if (d_summary == nullptr || ((d_x == nullptr) != (d_z == nullptr))) {
-    set_error("single ray: d_summary required, d_x/d_z both or neither");
+  if (int rc = null_argument("single ray", {{"m", m}, {"d_summary", d_summary}})) return rc;
+  if ((d_x == nullptr) != (d_z == nullptr)) {
+    set_error("single ray: d_x/d_z both or neither");
     return AIRICE_EINVAL;
   }
   DevMedium M;
   int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);  // RayTracingFunctions pi (.h:26)
   if (rc) return rc;
-  rc = launch_single_ray(M, m, antenna_depth_m, launch_deg, txh_m, ice_m, d_summary, d_x, d_z,
-                         cap, (hipStream_t)stream);
-  if (rc == AIRICE_EHIP) set_error("single ray launch failed: %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  return launch_single_ray(M, m, antenna_depth_m, launch_deg, txh_m, ice_m, d_summary, d_x, d_z,
+                           cap, (hipStream_t)stream);
 }
 
 double airice_nz_air(const airice_medium* m, double z) {
@@ -969,40 +854,13 @@ int airice_rtf_eval(const airice_medium* m, int op, const double* args, size_t n
 
 int airice_rtf_eval_variant(const airice_medium* m, int variant, int op, const double* args,
                             size_t n_args, double* out, size_t n_out) {
-  if (airice::scalar_on_host()) {
-    if (m == nullptr || out == nullptr || (n_args > 0 && args == nullptr)) {
-      set_error("null argument");
-      return AIRICE_EINVAL;
-    }
-    if (variant != AIRICE_VARIANT_MULTIRAY && variant != AIRICE_VARIANT_PYWRAPPER) {
-      set_error("unknown variant %d", variant);
-      return AIRICE_EINVAL;
-    }
-    const DevMedium* M = nullptr;
-    if (int rc = airice::folded_medium(m, variant, &M)) return rc;
-    const int need = airice::rtf_outputs(op, M->ml);
-    if (need < 0) {
-      set_error("unknown RayTracingFunctions op %d", op);
-      return AIRICE_EINVAL;
-    }
-    if (n_out < (size_t)need || n_args > 8) {
-      set_error("rtf op %d: %zu outputs (need %d), %zu args (max 8)", op, n_out, need, n_args);
-      return AIRICE_EINVAL;
-    }
-    return airice::rtf_host(*M, op, args, n_args, out);
-  }
-  if (m == nullptr || out == nullptr || (n_args > 0 && args == nullptr)) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
-  if (variant != AIRICE_VARIANT_MULTIRAY && variant != AIRICE_VARIANT_PYWRAPPER) {
-    set_error("unknown variant %d", variant);
-    return AIRICE_EINVAL;
-  }
-  DevMedium M;
-  int rc = build_dev_medium(m, variant, &M);
-  if (rc) return rc;
-  const int need = airice::rtf_outputs(op, M.ml);
+  if (int rc = null_argument("rtf", {{"m", m}, {"out", out}})) return rc;
+  if (n_args > 0)
+    if (int rc = null_argument("rtf", {{"args", args}})) return rc;
+  if (int rc = bad_variant("rtf", variant)) return rc;
+  const DevMedium* M = nullptr;
+  if (int rc = airice::folded_medium(m, variant, &M)) return rc;
+  const int need = airice::rtf_outputs(op, M->ml);
   if (need < 0) {
     set_error("unknown RayTracingFunctions op %d", op);
     return AIRICE_EINVAL;
@@ -1011,63 +869,38 @@ int airice_rtf_eval_variant(const airice_medium* m, int variant, int op, const d
     set_error("rtf op %d: %zu outputs (need %d), %zu args (max 8)", op, n_out, need, n_args);
     return AIRICE_EINVAL;
   }
-  ScalarCall call;  // the kernel writes its outputs straight into the pinned slot
-  if (!call.ok()) return AIRICE_EHIP;
-  call.arm();
-  rc = airice::launch_rtf(M, op, args, n_args, call.slot().d, call.slot().st);
-  if (rc) {
-    set_error("rtf launch failed: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
-  }
-  if ((rc = call.sync())) return rc;
-  std::memcpy(out, call.slot().h, sizeof(double) * need);
-  return AIRICE_OK;
-}
-
-// The null argument of an air2ice call, or nullptr when every required pointer is given.
-static const char* air2ice_null_arg(const void* m, const void* txh, const void* dist,
-                                    const void* ice, const void* depth, const void* out) {
-  return m == nullptr ? "m" : txh == nullptr ? "txh" : dist == nullptr ? "dist"
-       : ice == nullptr ? "ice" : depth == nullptr ? "depth" : out == nullptr ? "out" : nullptr;
+  if (airice::scalar_on_host()) return airice::rtf_host(*M, op, args, n_args, out);
+  // the inputs travel in the kernel arguments; the kernel writes its outputs into the slot
+  const DevMedium Md = *M;  // the launch's own copy: the fold cache is the thread's
+  return slot_call(nullptr, 0, 0, out, need, nullptr, 0, 0, [&](const SlotArgs& s) {
+    return airice::launch_rtf(Md, op, args, n_args, s.out, s.st);
+  });
 }
 
 int airice_air2ice_launch(const airice_medium* m, const double* d_txh, const double* d_dist,
                           const double* d_ice, const double* d_depth, size_t n, double* d_out,
                           size_t ld, uint8_t* d_status, void* stream) {
   if (n == 0) return AIRICE_OK;
-  if (const char* a = air2ice_null_arg(m, d_txh, d_dist, d_ice, d_depth, d_out)) {
-    set_error("air2ice: null argument (%s)", a);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("air2ice: ld (%zu) < n (%zu)", ld, n);
-    return AIRICE_EINVAL;
-  }
-  if (n > (size_t)0x7fffffff * 256) {
-    set_error("air2ice: n = %zu exceeds one launch", n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("air2ice", {{"m", m}, {"txh", d_txh}, {"dist", d_dist}, {"ice", d_ice},
+                                         {"depth", d_depth}, {"out", d_out}}))
+    return rc;
+  if (int rc = short_stride("air2ice", "ld", ld, n)) return rc;
+  if (int rc = exceeds_one_launch("air2ice", n)) return rc;
   DevMedium M;
   int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);  // RayTracingFunctions pi (.h:26)
   if (rc) return rc;
-  rc = airice::launch_air2ice(M, d_txh, d_dist, d_ice, d_depth, n, d_out, ld, d_status,
-                              (hipStream_t)stream);
-  if (rc) set_error("air2ice launch failed: %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  return airice::launch_air2ice(M, d_txh, d_dist, d_ice, d_depth, n, d_out, ld, d_status,
+                                (hipStream_t)stream);
 }
 
 int airice_air2ice_host(const airice_medium* m, const double* txh, const double* dist,
                         const double* ice, const double* depth, size_t n, double* out, size_t ld,
                         uint8_t* status) {
   if (n == 0) return AIRICE_OK;
-  if (const char* a = air2ice_null_arg(m, txh, dist, ice, depth, out)) {
-    set_error("air2ice: null argument (%s)", a);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("air2ice: ld (%zu) < n (%zu)", ld, n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("air2ice", {{"m", m}, {"txh", txh}, {"dist", dist}, {"ice", ice},
+                                         {"depth", depth}, {"out", out}}))
+    return rc;
+  if (int rc = short_stride("air2ice", "ld", ld, n)) return rc;
   constexpr int kF = AIRICE_RTF_AIR2ICE_FIELDS;
   if (n == 1) {  // one query: where airice_scalar_mode says
     const double in[4] = {txh[0], dist[0], ice[0], depth[0]};
@@ -1077,128 +910,68 @@ int airice_air2ice_host(const airice_medium* m, const double* txh, const double*
       const DevMedium* M = nullptr;
       if (int rc = airice::folded_medium(m, AIRICE_VARIANT_MULTIRAY, &M)) return rc;
       airice::air2ice_host_one(*M, in, o, &st);
-    } else {
-      const int rc = airice::slot_call(
-          in, 4, 0, o, kF, &st, 1, [&](const double* d, double* q, uint8_t* f, hipStream_t s) {
-            return airice_air2ice_launch(m, d, d + 1, d + 2, d + 3, 1, q, 1, f, s);
-          });
-      if (rc) return rc;
+    } else if (int rc = slot_call(in, 4, 0, o, kF, &st, 1, kNoSignal, [&](const SlotArgs& s) {
+                 return airice_air2ice_launch(m, s.in, s.in + 1, s.in + 2, s.in + 3, 1, s.out, 1,
+                                              s.flag, s.st);
+               })) {
+      return rc;
     }
-    for (int c = 0; c < kF; ++c) out[(size_t)c * ld] = o[c];
-    if (status) status[0] = st;
+    scatter_one(o, kF, st, out, ld, status);
     return AIRICE_OK;
   }
-  // one device block: txh | dist | ice | depth | out (16 x n) | status
-  DevBuffer buf;
-  HIP_TRY(buf.alloc(sizeof(double) * (4 + kF) * n + n));
-  double* din = static_cast<double*>(buf.p);
-  double* dout = din + 4 * n;
-  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)kF * n);
-  const double* src[4] = {txh, dist, ice, depth};
-  for (int k = 0; k < 4; ++k)
-    HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
-  const int rc = airice_air2ice_launch(m, din, din + n, din + 2 * n, din + 3 * n, n, dout, n, dst,
-                                       nullptr);
-  if (rc) return rc;
-  // the copy-back is on the null stream, like the launch: it waits for the kernel
-  HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
-                      hipMemcpyDeviceToHost));
-  if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
-  return AIRICE_OK;
+  const double* cols[4] = {txh, dist, ice, depth};
+  return staged_call(cols, 4, n, 0, kF, out, ld, status, [&](const Staged& s) {
+    return airice_air2ice_launch(m, s.col(0), s.col(1), s.col(2), s.col(3), n, s.out, n, s.status,
+                                 nullptr);
+  });
 }
 
 // ---- the in-ice solver (IceRayTracing::IceRayTracing), batched ---------------------------------
-static const double kIceRayDefaultModel[3] = {1.78, -0.43, 0.0132};  // IceRayTracing.hh:52-54
-
-// The null argument of an iceray call, or nullptr when every required pointer is given.
-static const char* iceray_null_arg(const void* z0, const void* x1, const void* z1,
-                                   const void* out) {
-  return z0 == nullptr ? "z0" : x1 == nullptr ? "x1" : z1 == nullptr ? "z1"
-       : out == nullptr ? "out" : nullptr;
-}
-
 int airice_iceray_launch(const double* model3, const double* d_z0, const double* d_x1,
                          const double* d_z1, size_t n, double* d_out, size_t ld,
                          uint8_t* d_status, void* stream) {
   if (n == 0) return AIRICE_OK;
-  if (const char* a = iceray_null_arg(d_z0, d_x1, d_z1, d_out)) {
-    set_error("iceray: null argument (%s)", a);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("iceray: ld (%zu) < n (%zu)", ld, n);
-    return AIRICE_EINVAL;
-  }
-  if (n > (size_t)0x7fffffff * 256) {
-    set_error("iceray: n = %zu exceeds one launch", n);
-    return AIRICE_EINVAL;
-  }
-  const int rc = airice::launch_iceray(model3 != nullptr ? model3 : kIceRayDefaultModel, d_z0,
-                                       d_x1, d_z1, n, d_out, ld, d_status, (hipStream_t)stream);
-  if (rc) set_error("iceray launch failed: %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  if (int rc = null_argument("iceray", {{"z0", d_z0}, {"x1", d_x1}, {"z1", d_z1}, {"out", d_out}}))
+    return rc;
+  if (int rc = short_stride("iceray", "ld", ld, n)) return rc;
+  if (int rc = exceeds_one_launch("iceray", n)) return rc;
+  return airice::launch_iceray(ice_model_or_default(model3), d_z0, d_x1, d_z1, n, d_out, ld,
+                               d_status, (hipStream_t)stream);
 }
 
 int airice_iceray_host(const double* model3, const double* z0, const double* x1, const double* z1,
                        size_t n, double* out, size_t ld, uint8_t* status) {
   if (n == 0) return AIRICE_OK;
-  if (const char* a = iceray_null_arg(z0, x1, z1, out)) {
-    set_error("iceray: null argument (%s)", a);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("iceray: ld (%zu) < n (%zu)", ld, n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("iceray", {{"z0", z0}, {"x1", x1}, {"z1", z1}, {"out", out}}))
+    return rc;
+  if (int rc = short_stride("iceray", "ld", ld, n)) return rc;
   constexpr int kF = AIRICE_ICERAY_FIELDS;
   if (n == 1) {  // one pair: where airice_scalar_mode says
     const double in[3] = {z0[0], x1[0], z1[0]};
     double o[kF];
     uint8_t st = 0;
     if (airice::scalar_on_host()) {
-      airice::iceray_host_one(model3 != nullptr ? model3 : kIceRayDefaultModel, in, o, &st);
-    } else {
-      // the scalar slot: inputs at h[0..2], the 32 outputs from h[8], the status byte at h + 48
-      constexpr int kOut = 8, kFlag = 48;
-      static_assert(kOut + kF <= kFlag && kFlag < (int)airice::kScalarSlotDoubles, "slot layout");
-      airice::ScalarCall call;
-      if (!call.ok()) return AIRICE_EHIP;
-      airice::ScalarSlot& s = call.slot();
-      std::copy(in, in + 3, s.h);
-      int rc = airice_iceray_launch(model3, s.d, s.d + 1, s.d + 2, 1, s.d + kOut, 1,
-                                    reinterpret_cast<uint8_t*>(s.d + kFlag), s.st);
-      if (rc == AIRICE_OK) rc = call.sync();
-      if (rc) return rc;
-      std::copy(s.h + kOut, s.h + kOut + kF, o);
-      st = *reinterpret_cast<const uint8_t*>(s.h + kFlag);
+      airice::iceray_host_one(ice_model_or_default(model3), in, o, &st);
+    } else if (int rc = slot_call(in, 3, 0, o, kF, &st, 1, kNoSignal, [&](const SlotArgs& s) {
+                 return airice_iceray_launch(model3, s.in, s.in + 1, s.in + 2, 1, s.out, 1, s.flag,
+                                             s.st);
+               })) {
+      return rc;
     }
-    for (int c = 0; c < kF; ++c) out[(size_t)c * ld] = o[c];
-    if (status) status[0] = st;
+    scatter_one(o, kF, st, out, ld, status);
     return AIRICE_OK;
   }
-  // one device block: z0 | x1 | z1 | out (32 x n) | status
-  DevBuffer buf;
-  HIP_TRY(buf.alloc(sizeof(double) * (3 + kF) * n + n));
-  double* din = static_cast<double*>(buf.p);
-  double* dout = din + 3 * n;
-  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)kF * n);
-  const double* src[3] = {z0, x1, z1};
-  for (int k = 0; k < 3; ++k)
-    HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
-  const int rc = airice_iceray_launch(model3, din, din + n, din + 2 * n, n, dout, n, dst, nullptr);
-  if (rc) return rc;
-  // the copy-back is on the null stream, like the launch: it waits for the kernel
-  HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
-                      hipMemcpyDeviceToHost));
-  if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
-  return AIRICE_OK;
+  const double* cols[3] = {z0, x1, z1};
+  return staged_call(cols, 3, n, 0, kF, out, ld, status, [&](const Staged& s) {
+    return airice_iceray_launch(model3, s.col(0), s.col(1), s.col(2), n, s.out, n, s.status,
+                                nullptr);
+  });
 }
 
 // ---- GetRayTracingSolutions / GetFocusingFactor over the solver's rows --------------------------
 // What is wrong with the values of an icesol call (set as the error), or false.
 static bool icesol_refuses(const double* model3, double a0, double frequency_ghz) {
-  const char* bad = airice::icesol_bad_value(model3 != nullptr ? model3 : kIceRayDefaultModel, a0,
-                                             frequency_ghz);
+  const char* bad = airice::icesol_bad_value(ice_model_or_default(model3), a0, frequency_ghz);
   if (bad != nullptr) set_error("icesol: %s", bad);
   return bad != nullptr;
 }
@@ -1209,27 +982,34 @@ int airice_icesol_launch(const double* model3, const double* d_z0, const double*
                          double frequency_ghz, double* d_out, size_t ld, uint8_t* d_status,
                          void* stream) {
   if (n == 0) return AIRICE_OK;
-  const char* a = iceray_null_arg(d_z0, d_x1, d_z1, d_out);
-  if (a == nullptr && d_rays == nullptr) a = "rays";
-  if (a != nullptr) {
-    set_error("icesol: null argument (%s)", a);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n || ld_rays < n || (d_rays_lower != nullptr && ld_lower < n)) {
-    set_error("icesol: %s (%zu) < n (%zu)", ld < n ? "ld" : ld_rays < n ? "ld_rays" : "ld_lower",
-              ld < n ? ld : ld_rays < n ? ld_rays : ld_lower, n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("icesol", {{"z0", d_z0}, {"x1", d_x1}, {"z1", d_z1}, {"out", d_out},
+                                        {"rays", d_rays}}))
+    return rc;
+  if (int rc = short_stride("icesol", "ld", ld, n)) return rc;
+  if (int rc = short_stride("icesol", "ld_rays", ld_rays, n)) return rc;
+  if (d_rays_lower != nullptr)
+    if (int rc = short_stride("icesol", "ld_lower", ld_lower, n)) return rc;
   if (icesol_refuses(model3, a0, frequency_ghz)) return AIRICE_EINVAL;
-  if (n > (size_t)0x7fffffff * 256) {
-    set_error("icesol: n = %zu exceeds one launch", n);
-    return AIRICE_EINVAL;
-  }
-  const int rc = airice::launch_icesol(model3 != nullptr ? model3 : kIceRayDefaultModel, a0,
-                                       frequency_ghz, d_z0, d_x1, d_z1, d_rays, ld_rays,
-                                       d_rays_lower, ld_lower, n, d_out, ld, d_status,
-                                       (hipStream_t)stream);
-  if (rc) set_error("icesol launch failed: %s", hipGetErrorString(hipGetLastError()));
+  if (int rc = exceeds_one_launch("icesol", n)) return rc;
+  return airice::launch_icesol(ice_model_or_default(model3), a0, frequency_ghz, d_z0, d_x1, d_z1,
+                               d_rays, ld_rays, d_rays_lower, ld_lower, n, d_out, ld, d_status,
+                               (hipStream_t)stream);
+}
+
+// The launches of one icesol call on device arrays of stride n: the solver's rows for the
+// receiver into rays, for the receiver 1 cm lower (z1_lower; null: no focusing) into rays + 32 n,
+// then the solutions.
+static int icesol_launches(const double* model3, const double* z0, const double* x1,
+                           const double* z1, const double* z1_lower, double* rays, size_t n,
+                           double a0, double frequency_ghz, double* out, uint8_t* status,
+                           hipStream_t st) {
+  double* lower = z1_lower != nullptr ? rays + (size_t)AIRICE_ICERAY_FIELDS * n : nullptr;
+  int rc = airice_iceray_launch(model3, z0, x1, z1, n, rays, n, nullptr, st);
+  if (rc == AIRICE_OK && lower != nullptr)
+    rc = airice_iceray_launch(model3, z0, x1, z1_lower, n, lower, n, nullptr, st);
+  if (rc == AIRICE_OK)
+    rc = airice_icesol_launch(model3, z0, x1, z1, rays, n, lower, n, n, a0, frequency_ghz, out, n,
+                              status, st);
   return rc;
 }
 
@@ -1237,85 +1017,48 @@ int airice_icesol_host(const double* model3, const double* z0, const double* x1,
                        size_t n, double a0, double frequency_ghz, int focusing, double* out,
                        size_t ld, uint8_t* status) {
   if (n == 0) return AIRICE_OK;
-  if (const char* a = iceray_null_arg(z0, x1, z1, out)) {
-    set_error("icesol: null argument (%s)", a);
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("icesol: ld (%zu) < n (%zu)", ld, n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("icesol", {{"z0", z0}, {"x1", x1}, {"z1", z1}, {"out", out}}))
+    return rc;
+  if (int rc = short_stride("icesol", "ld", ld, n)) return rc;
   if (icesol_refuses(model3, a0, frequency_ghz)) return AIRICE_EINVAL;
   constexpr int kF = AIRICE_ICESOL_FIELDS, kR = AIRICE_ICERAY_FIELDS;
   const bool focus = focusing != 0;
   if (n == 1) {  // one pair: where airice_scalar_mode says
-    const double in[3] = {z0[0], x1[0], z1[0]};
+    const double in[4] = {z0[0], x1[0], z1[0], z1[0] - 0.01};
     double o[kF];
     uint8_t st = 0;
     if (airice::scalar_on_host()) {
-      airice::icesol_host_one(model3 != nullptr ? model3 : kIceRayDefaultModel, in, a0,
-                              frequency_ghz, focus, o, &st);
-    } else {
-      // the scalar slot: z0, x1, z1 and the lower z1 at h[0..3], the receiver's 32 columns from
-      // h[8], the lower receiver's from h[40], the 18 outputs from h[72], the status byte at h + 96
-      constexpr int kRays = 8, kLower = kRays + kR, kOut = kLower + kR, kFlag = 96;
-      static_assert(kOut + kF <= kFlag && kFlag < (int)airice::kScalarSlotDoubles, "slot layout");
-      airice::ScalarCall call;
-      if (!call.ok()) return AIRICE_EHIP;
-      airice::ScalarSlot& s = call.slot();
-      std::copy(in, in + 3, s.h);
-      s.h[3] = in[2] - 0.01;
-      int rc = airice_iceray_launch(model3, s.d, s.d + 1, s.d + 2, 1, s.d + kRays, 1, nullptr, s.st);
-      if (rc == AIRICE_OK && focus)
-        rc = airice_iceray_launch(model3, s.d, s.d + 1, s.d + 3, 1, s.d + kLower, 1, nullptr, s.st);
-      if (rc == AIRICE_OK)
-        rc = airice_icesol_launch(model3, s.d, s.d + 1, s.d + 2, s.d + kRays, 1,
-                                  focus ? s.d + kLower : nullptr, 1, 1, a0, frequency_ghz,
-                                  s.d + kOut, 1, reinterpret_cast<uint8_t*>(s.d + kFlag), s.st);
-      if (rc == AIRICE_OK) rc = call.sync();
-      if (rc) return rc;
-      std::copy(s.h + kOut, s.h + kOut + kF, o);
-      st = *reinterpret_cast<const uint8_t*>(s.h + kFlag);
+      airice::icesol_host_one(ice_model_or_default(model3), in, a0, frequency_ghz, focus, o, &st);
+    } else if (int rc = slot_call(in, 4, 2 * kR, o, kF, &st, 1, kNoSignal,  // up to three launches
+                                  [&](const SlotArgs& s) {
+                                    return icesol_launches(model3, s.in, s.in + 1, s.in + 2,
+                                                           focus ? s.in + 3 : nullptr, s.scratch, 1,
+                                                           a0, frequency_ghz, s.out, s.flag, s.st);
+                                  })) {
+      return rc;
     }
-    for (int c = 0; c < kF; ++c) out[(size_t)c * ld] = o[c];
-    if (status) status[0] = st;
+    scatter_one(o, kF, st, out, ld, status);
     return AIRICE_OK;
   }
-  // one device block: z0 | x1 | z1 | z1 - 0.01 | rays (32 x n) | lower rays (32 x n) | out
-  // (18 x n) | status
-  const size_t n_rays = focus ? 2 : 1;
-  DevBuffer buf;
-  HIP_TRY(buf.alloc(sizeof(double) * (4 + n_rays * kR + kF) * n + n));
-  double* din = static_cast<double*>(buf.p);
-  double* drays = din + 4 * n;
-  double* dlower = focus ? drays + (size_t)kR * n : nullptr;
-  double* dout = drays + n_rays * kR * n;
-  uint8_t* dst = reinterpret_cast<uint8_t*>(dout + (size_t)kF * n);
-  const double* src[3] = {z0, x1, z1};
-  for (int k = 0; k < 3; ++k)
-    HIP_TRY(hipMemcpy(din + k * n, src[k], sizeof(double) * n, hipMemcpyHostToDevice));
-  int rc = airice_iceray_launch(model3, din, din + n, din + 2 * n, n, drays, n, nullptr, nullptr);
-  if (rc) return rc;
+  // the fourth input column is the receiver 1 cm lower (GetFocusingFactor), formed here
+  std::vector<double> lower;
   if (focus) {
-    std::vector<double> lower(z1, z1 + n);
+    lower = std::vector<double>(z1, z1 + n);
     for (double& v : lower) v = v - 0.01;
-    HIP_TRY(hipMemcpy(din + 3 * n, lower.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-    rc = airice_iceray_launch(model3, din, din + n, din + 3 * n, n, dlower, n, nullptr, nullptr);
-    if (rc) return rc;
   }
-  rc = airice_icesol_launch(model3, din, din + n, din + 2 * n, drays, n, dlower, n, n, a0,
-                            frequency_ghz, dout, n, dst, nullptr);
-  if (rc) return rc;
-  // the copy-back is on the null stream, like the launches: it waits for the kernels
-  HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, dout, sizeof(double) * n, sizeof(double) * n, kF,
-                      hipMemcpyDeviceToHost));
-  if (status) HIP_TRY(hipMemcpy(status, dst, n, hipMemcpyDeviceToHost));
-  return AIRICE_OK;
+  const double* cols[4] = {z0, x1, z1, lower.data()};
+  return staged_call(cols, focus ? 4 : 3, n, (focus ? 2 : 1) * (size_t)kR * n, kF, out, ld, status,
+                     [&](const Staged& s) {
+                       return icesol_launches(model3, s.col(0), s.col(1), s.col(2),
+                                              focus ? s.col(3) : nullptr, s.scratch, n, a0,
+                                              frequency_ghz, s.out, s.status, nullptr);
+                     });
 }
 
 int airice_single_ray_host(const airice_medium* m, double antenna_depth_m, double launch_deg,
                            double txh_m, double ice_m, double* summary, double* x, double* z,
                            size_t cap) {
+  if (int rc = null_argument("single ray", {{"summary", summary}})) return rc;
   airice_single_ray_info info;
   int rc = airice_single_ray_plan(m, antenna_depth_m, launch_deg, txh_m, ice_m, &info);
   if (rc) return rc;
@@ -1332,26 +1075,28 @@ int airice_single_ray_host(const airice_medium* m, double antenna_depth_m, doubl
   double* dx = path ? d + AIRICE_SINGLE_RAY_WORK : nullptr;
   double* dz = path ? dx + n : nullptr;
   rc = airice_single_ray_launch(m, antenna_depth_m, launch_deg, txh_m, ice_m, d, dx, dz, n, nullptr);
-  if (rc == AIRICE_OK) {
-    hipError_t e = hipMemcpy(summary, d, sizeof(double) * AIRICE_SINGLE_RAY_FIELDS,
-                             hipMemcpyDeviceToHost);
-    if (e == hipSuccess && path && n > 0) e = hipMemcpy(x, dx, sizeof(double) * n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && path && n > 0) e = hipMemcpy(z, dz, sizeof(double) * n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-      set_error("single ray copy failed: %s", hipGetErrorString(e));
-      rc = AIRICE_EHIP;
-    }
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(summary, d, sizeof(double) * AIRICE_SINGLE_RAY_FIELDS, hipMemcpyDeviceToHost));
+  if (path && n > 0) {
+    HIP_TRY(hipMemcpy(x, dx, sizeof(double) * n, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(z, dz, sizeof(double) * n, hipMemcpyDeviceToHost));
   }
-  return rc;
+  return AIRICE_OK;
 }
 
 int airice_ray_paths_plan(const airice_medium* m, double antenna_depth_m, double ice_m,
                           const double* txh_m, size_t n, int64_t* offsets, size_t* work_bytes) {
-  if (m == nullptr || offsets == nullptr || (n > 0 && txh_m == nullptr)) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("ray paths", {{"m", m}, {"offsets", offsets}})) return rc;
+  if (n > 0)
+    if (int rc = null_argument("ray paths", {{"txh_m", txh_m}})) return rc;
   return plan_ray_paths(m, antenna_depth_m, ice_m, txh_m, n, offsets, work_bytes);
+}
+
+// x and z of a ray-paths call are given together or not at all.
+static int ray_paths_xz(const void* x, const void* z) {
+  if ((x == nullptr) == (z == nullptr)) return AIRICE_OK;
+  set_error("ray paths: x / z both or neither");
+  return AIRICE_EINVAL;
 }
 
 int airice_ray_paths_launch(const airice_medium* m, double antenna_depth_m, double ice_m,
@@ -1360,22 +1105,17 @@ int airice_ray_paths_launch(const airice_medium* m, double antenna_depth_m, doub
                             double* d_summary, size_t ld, double* d_x, double* d_z, size_t cap,
                             void* stream) {
   if (n == 0) return AIRICE_OK;
-  if (m == nullptr || d_launch_deg == nullptr || txh_m == nullptr || offsets == nullptr ||
-      d_work == nullptr || d_summary == nullptr || ((d_x == nullptr) != (d_z == nullptr))) {
-    set_error("ray paths: null argument (d_x/d_z both or neither)");
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("ray paths: summary stride %zu is less than %zu rays", ld, n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("ray paths", {{"m", m}, {"d_launch_deg", d_launch_deg},
+                                           {"txh_m", txh_m}, {"offsets", offsets},
+                                           {"d_work", d_work}, {"d_summary", d_summary}}))
+    return rc;
+  if (int rc = ray_paths_xz(d_x, d_z)) return rc;
+  if (int rc = short_stride("ray paths", "ld", ld, n)) return rc;
   DevMedium M;
   int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);  // RayTracingFunctions pi (.h:26)
   if (rc) return rc;
-  rc = launch_ray_paths(M, m, antenna_depth_m, ice_m, d_launch_deg, txh_m, n, offsets, d_work,
-                        work_bytes, d_summary, ld, d_x, d_z, cap, (hipStream_t)stream);
-  if (rc == AIRICE_EHIP) set_error("ray paths launch failed: %s", hipGetErrorString(hipGetLastError()));
-  return rc;
+  return launch_ray_paths(M, m, antenna_depth_m, ice_m, d_launch_deg, txh_m, n, offsets, d_work,
+                          work_bytes, d_summary, ld, d_x, d_z, cap, (hipStream_t)stream);
 }
 
 int airice_ray_paths_host(const airice_medium* m, double antenna_depth_m, double ice_m,
@@ -1383,15 +1123,11 @@ int airice_ray_paths_host(const airice_medium* m, double antenna_depth_m, double
                           const int64_t* offsets, double* summary, size_t ld, double* x, double* z,
                           size_t cap) {
   if (n == 0) return AIRICE_OK;
-  if (m == nullptr || launch_deg == nullptr || txh_m == nullptr || offsets == nullptr ||
-      summary == nullptr || ((x == nullptr) != (z == nullptr))) {
-    set_error("ray paths: null argument (x/z both or neither)");
-    return AIRICE_EINVAL;
-  }
-  if (ld < n) {
-    set_error("ray paths: summary stride %zu is less than %zu rays", ld, n);
-    return AIRICE_EINVAL;
-  }
+  if (int rc = null_argument("ray paths", {{"m", m}, {"launch_deg", launch_deg}, {"txh_m", txh_m},
+                                           {"offsets", offsets}, {"summary", summary}}))
+    return rc;
+  if (int rc = ray_paths_xz(x, z)) return rc;
+  if (int rc = short_stride("ray paths", "ld", ld, n)) return rc;
   std::vector<int64_t> planned(n + 1);
   size_t work_bytes = 0;
   int rc = plan_ray_paths(m, antenna_depth_m, ice_m, txh_m, n, planned.data(), &work_bytes);
@@ -1426,37 +1162,32 @@ int airice_ray_paths_host(const airice_medium* m, double antenna_depth_m, double
 int airice_trace_ice_to_air_launch(const airice_medium* m, const double* d_depth,
                                    const double* d_ice, const double* d_txh, const double* d_dist,
                                    size_t n, double* d_out10, void* stream) {
+  if (n > 0)
+    if (int rc = null_argument("trace", {{"m", m}, {"d_depth", d_depth}, {"d_ice", d_ice},
+                                         {"d_txh", d_txh}, {"d_dist", d_dist},
+                                         {"d_out10", d_out10}}))
+      return rc;
   DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_PYWRAPPER, &M);
-  if (rc) return rc;
   IceConsts I;
-  build_ice_consts(M, 0.0, 0.0, &I);
+  if (int rc = launch_folds(m, AIRICE_VARIANT_PYWRAPPER, 0.0, 0.0, &M, &I)) return rc;
   return launch_trace(M, I, d_depth, d_ice, d_txh, d_dist, n, d_out10, (hipStream_t)stream);
 }
 
 int airice_trace_ice_to_air_host(const airice_medium* m, const double* depth, const double* ice,
                                  const double* txh, const double* dist, size_t n, double* out10) {
   if (n == 0) return AIRICE_OK;
-  if (m == nullptr || depth == nullptr || ice == nullptr || txh == nullptr || dist == nullptr ||
-      out10 == nullptr) {
-    set_error("null argument");
-    return AIRICE_EINVAL;
-  }
-  if (n == 1 && airice::scalar_on_host()) {  // one query: on the host (airice_scalar_mode)
+  if (int rc = null_argument("trace", {{"m", m}, {"depth", depth}, {"ice", ice}, {"txh", txh},
+                                       {"dist", dist}, {"out10", out10}}))
+    return rc;
+  if (n == 1) {  // one query: where airice_scalar_mode says
     const double in[4] = {depth[0], ice[0], txh[0], dist[0]};
     return airice::trace_one(m, in, out10);
   }
-  DevBuffer mem;
-  HIP_TRY(mem.alloc(sizeof(double) * 14 * n));
-  double* buf = static_cast<double*>(mem.p);
-  double *dd = buf, *di = buf + n, *dt = buf + 2 * n, *ds = buf + 3 * n, *dout = buf + 4 * n;
-  HIP_TRY(hipMemcpy(dd, depth, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(di, ice, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dt, txh, sizeof(double) * n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ds, dist, sizeof(double) * n, hipMemcpyHostToDevice));
-  int rc = airice_trace_ice_to_air_launch(m, dd, di, dt, ds, n, dout, nullptr);
-  if (rc == AIRICE_OK) HIP_TRY(hipMemcpy(out10, dout, sizeof(double) * 10 * n, hipMemcpyDeviceToHost));
-  return rc;
+  const double* cols[4] = {depth, ice, txh, dist};
+  return staged_call(cols, 4, n, 0, 10, out10, n, nullptr, [&](const Staged& s) {
+    return airice_trace_ice_to_air_launch(m, s.col(0), s.col(1), s.col(2), s.col(3), n, s.out,
+                                          nullptr);
+  });
 }
 
 int airice_device_count(int* count) {

@@ -514,11 +514,9 @@ static int launch_roots(const DevMedium& M, const IceConsts& I, const QueryArgs&
   const size_t group_min = group_min_batch(IN);
   if (group_min == 0 || n < group_min ||
       park.stats != nullptr || n >= (1ull << 31)) {
-    ktimer_begin(KT_ROOTS, st);
-    count_launch(LC_ROOTS);
-    hipLaunchKernelGGL((roots_kernel<IN>), roots_grid(n), dim3(kRootsBlock), 0, st, M, I, Q, park);
-    ktimer_end(KT_ROOTS, st);
-    return launch_ok();
+    return bracket_launch(LC_ROOTS, KT_ROOTS, st, [&] {
+      hipLaunchKernelGGL((roots_kernel<IN>), roots_grid(n), dim3(kRootsBlock), 0, st, M, I, Q, park);
+    });
   }
   const GroupKey& thresholds = group_thresholds();
   // at most kGroupBlocks blocks in the two passes (each scatter block reads every block's
@@ -579,10 +577,10 @@ template <int OUT>
 static int launch_one_wave(const DevMedium& M, const IceConsts& I, const QueryArgs& Q,
                            const Park& park, double* out, size_t ld, uint8_t* flag,
                            hipStream_t st) {
-  count_launch(LC_SCALAR_SOLVE);
-  hipLaunchKernelGGL((scalar_solve_kernel<EntryPoint<OUT>::in, OUT>), dim3(1), dim3(64), 0, st, M,
-                     I, Q, park, out, ld, flag, take_scalar_signal());
-  return launch_ok();
+  return bracket_launch(LC_SCALAR_SOLVE, kNoTimer, st, [&] {
+    hipLaunchKernelGGL((scalar_solve_kernel<EntryPoint<OUT>::in, OUT>), dim3(1), dim3(64), 0, st, M,
+                       I, Q, park, out, ld, flag, take_scalar_signal());
+  });
 }
 
 // A minimizer launch of entry point OUT on one stream.  One query takes the one-wave kernel
@@ -601,11 +599,8 @@ static int launch_entry(const DevMedium& M, const IceConsts& I, const QueryArgs&
   if (int rc = launch_roots<EntryPoint<OUT>::in>(M, I, Q, park, (size_t)Q.n, st, sp, scr.ws))
     return rc;
   if (int rc = between()) return rc;
-  ktimer_begin(KT_OUT, st);
-  count_launch(LC_OUT);
-  stage2(dim3(grid_for(Q.n)), dim3(kBlock), sp);
-  ktimer_end(KT_OUT, st);
-  const int rc = launch_ok();
+  const int rc = bracket_launch(LC_OUT, KT_OUT, st,
+                                [&] { stage2(dim3(grid_for(Q.n)), dim3(kBlock), sp); });
   if (int rf = scr.release()) return rf;
   return rc;
 }
@@ -789,12 +784,10 @@ int launch_lookup(const DevMedium& M, const IceConsts& I, const airice_lookup_ta
   const LkTable T = lk_table(t);
   const QueryArgs Q{src, dist, depth, nullptr, fallback_ice_arg(ice_cm), (long long)n, flags};
   const unsigned grid = (unsigned)((n + kLkBlock - 1) / kLkBlock);
-  ktimer_begin(KT_LOOKUP, st);
-  count_launch(LC_LOOKUP);
-  hipLaunchKernelGGL(lookup_kernel, dim3(grid), dim3(kLkBlock), 0, st, T, M, I, Q, out, ld, ok,
-                     flags, bisect_exact());
-  ktimer_end(KT_LOOKUP, st);
-  return launch_ok();
+  return bracket_launch(LC_LOOKUP, KT_LOOKUP, st, [&] {
+    hipLaunchKernelGGL(lookup_kernel, dim3(grid), dim3(kLkBlock), 0, st, T, M, I, Q, out, ld, ok,
+                       flags, bisect_exact());
+  });
 }
 
 size_t lookup_multi_work_bytes(size_t n_tables, size_t n_ant) {
@@ -815,8 +808,10 @@ int launch_lookup_multi(const DevMedium& M, const IceConsts& I, const airice_loo
   for (int t = 0; t < n_tables; ++t) ht[t] = lk_table(tables + t);
   for (size_t a = 0; a < n_ant; ++a) ha[a] = LkAntenna{antenna_depth_cm[a], antenna_table[a], 0};
   // (a copy from pageable memory returns once the source has been read)
-  if (hipMemcpyAsync(d_work, img.data(), img.size(), hipMemcpyHostToDevice, st) != hipSuccess)
+  if (hipError_t e = hipMemcpyAsync(d_work, img.data(), img.size(), hipMemcpyHostToDevice, st)) {
+    set_error("lookup multi: workspace upload failed: %s", hipGetErrorString(e));
     return AIRICE_EHIP;
+  }
   const LkTableDev* d_tabs = static_cast<const LkTableDev*>(d_work);
   const LkAntenna* d_ants =
       reinterpret_cast<const LkAntenna*>(static_cast<const char*>(d_work) + tab_bytes);
@@ -824,12 +819,10 @@ int launch_lookup_multi(const DevMedium& M, const IceConsts& I, const airice_loo
   const unsigned gy = (unsigned)(n_ant < kMaxY ? n_ant : kMaxY);
   const dim3 grid((unsigned)((n_src + kLkBlock - 1) / kLkBlock), gy,
                   (unsigned)((n_ant + gy - 1) / gy));
-  ktimer_begin(KT_LOOKUP_MULTI, st);
-  count_launch(LC_LOOKUP_MULTI);
-  hipLaunchKernelGGL(lookup_multi_kernel, grid, dim3(kLkBlock), 0, st, d_tabs, d_ants, (int)n_ant,
-                     M, I, src, dist, ld_dist, fallback_ice_arg(ice_cm), (long long)n_src, out, ld,
-                     ok, flags, bisect_exact());
-  ktimer_end(KT_LOOKUP_MULTI, st);
-  return launch_ok();
+  return bracket_launch(LC_LOOKUP_MULTI, KT_LOOKUP_MULTI, st, [&] {
+    hipLaunchKernelGGL(lookup_multi_kernel, grid, dim3(kLkBlock), 0, st, d_tabs, d_ants, (int)n_ant,
+                       M, I, src, dist, ld_dist, fallback_ice_arg(ice_cm), (long long)n_src, out,
+                       ld, ok, flags, bisect_exact());
+  });
 }
 }  // namespace airice

@@ -874,33 +874,30 @@ int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_gri
     return rc;
   }
   const size_t lds_bytes = sizeof(RowConst) * (size_t)rpb;
-  ktimer_begin(KT_TABLE, st);
   const bool sc1 = (long long)blocks * kTableBlock < kAgentStoreRays;
   auto multi = M.A_air == 1.0 ? (sc1 ? table_multi_kernel<true, true> : table_multi_kernel<true, false>)
                               : (sc1 ? table_multi_kernel<false, true> : table_multi_kernel<false, false>);
-  count_launch(LC_TABLE);
-  hipLaunchKernelGGL(multi, dim3((unsigned)blocks), dim3(kTableBlock),
-                     lds_bytes, st, M, static_cast<const IceConsts*>(dconst),
-                     reinterpret_cast<const TableArgs*>(static_cast<unsigned char*>(dconst) +
-                                                        bytes_i),
-                     map);
-  ktimer_end(KT_TABLE, st);
-  return launch_ok();
+  return bracket_launch(LC_TABLE, KT_TABLE, st, [&] {
+    hipLaunchKernelGGL(multi, dim3((unsigned)blocks), dim3(kTableBlock), lds_bytes, st, M,
+                       static_cast<const IceConsts*>(dconst),
+                       reinterpret_cast<const TableArgs*>(static_cast<unsigned char*>(dconst) +
+                                                          bytes_i),
+                       map);
+  });
 }
 
 int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
                 int in_ice, size_t n, double* out, size_t ld, hipStream_t st) {
   if (n == 0) return AIRICE_OK;
-  if (n == 1) {  // one ray: spread over a wave (ray_solution_wave)
-    count_launch(LC_SCALAR_RAY);
-    hipLaunchKernelGGL(scalar_ray_kernel, dim3(1), dim3(64), 0, st, M, I, launch, txh, in_ice, out,
-                       ld, take_scalar_signal());
-    return launch_ok();
-  }
-  count_launch(LC_RAYS);
-  hipLaunchKernelGGL(rays_kernel, dim3(grid_for((long long)n)), dim3(kBlock), 0, st, M, I, launch,
-                     txh, in_ice, (long long)n, out, ld, Signal{});
-  return launch_ok();
+  if (n == 1)  // one ray: spread over a wave (ray_solution_wave)
+    return bracket_launch(LC_SCALAR_RAY, kNoTimer, st, [&] {
+      hipLaunchKernelGGL(scalar_ray_kernel, dim3(1), dim3(64), 0, st, M, I, launch, txh, in_ice,
+                         out, ld, take_scalar_signal());
+    });
+  return bracket_launch(LC_RAYS, kNoTimer, st, [&] {
+    hipLaunchKernelGGL(rays_kernel, dim3(grid_for((long long)n)), dim3(kBlock), 0, st, M, I, launch,
+                       txh, in_ice, (long long)n, out, ld, Signal{});
+  });
 }
 
 // The one-query GetRayTracingSolutions on the host (airice_rays_host): ray_solution compiled for

@@ -175,7 +175,13 @@ int airice_scalar_mode(int mode);
  * Air2IceRayTracing's StraightAngle argument (.cc:1464) in degrees; when NULL it is
  * formed per query as GetHorizontalDistanceToIntersectionPoint does (.cc:952-958).
  * d_out: AIRICE_SOLVE_FIELDS (MultiRay) or AIRICE_PYSOLVE_FIELDS (pythonwrapper)
- * double columns, stride ld.  d_status (nullable): AIRICE_SOLVE_* bits. */
+ * double columns, stride ld.  d_status (nullable): AIRICE_SOLVE_* bits.
+ * airice_solve_host is the same with every array on the host; with ld > n it writes entries
+ * [0, n) of each column only: the padding out[c*ld + n .. c*ld + ld) is left as the caller had
+ * it (earlier builds of the library overwrote it with undefined values).  n == 1 runs where
+ * airice_scalar_mode says: on the calling thread, or on the device through the scalar slot as
+ * every other one-query call does (earlier builds took the batch route's device block for it; the
+ * kernel and the bits are the same).  The same holds for airice_trace_ice_to_air_host. */
 int airice_solve_launch(const airice_medium *m, int variant, double ice_h_m,
                         const double *d_txh, const double *d_dist, const double *d_depth,
                         const double *d_straight_angle, size_t n, double *d_out, size_t ld,
