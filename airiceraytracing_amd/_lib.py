@@ -212,6 +212,8 @@ EXPORTED_SYMBOLS = (
     "airice_icetab_grid_init", "airice_icetab_grid", "airice_icetab_layout",
     "airice_icetab_pack_host", "airice_icetab_work_bytes", "airice_icetab_build_launch",
     "airice_icetab_build_host", "airice_icetab_lookup_launch", "airice_icetab_lookup_host",
+    "airice_icepath_plan", "airice_icepath_launch", "airice_icepath_host",
+    "airice_icepath_one_host",
     "Py_TraceIceToAir", "airice_device_count", "airice_set_device", "airice_malloc",
     "airice_free", "airice_memcpy_h2d", "airice_memcpy_d2h", "airice_synchronize",
     "airice_kernel_timing", "airice_kernel_time", "airice_launch_count",
@@ -305,6 +307,11 @@ def lib() -> ctypes.CDLL:
         "airice_icetab_build_host": ([P, P, P, S, D, D], I),
         "airice_icetab_lookup_launch": ([P, S, P, P, P, S, P, S, P, P], I),
         "airice_icetab_lookup_host": ([P, S, P, P, P, S, P, S, P], I),
+        "airice_icepath_plan": ([P, P, P, S, I, P, ctypes.POINTER(S)], I),
+        "airice_icepath_launch": ([P, P, P, P, P, S, P, P, P, S, I, P, P, S, P, P, P, S, P], I),
+        "airice_icepath_host": ([P, P, P, P, P, S, P, S, I, P, P, P, P, S], I),
+        "airice_icepath_one_host": ([P, I, D, D, D, D, D, P, P, S,
+                                     ctypes.POINTER(ctypes.c_int64)], I),
         "airice_table_to_host": ([P, S, S, P, S, P], I),
         "airice_host_register": ([P, S], I),
         "airice_host_unregister": ([P], I),

@@ -12,6 +12,7 @@
 
 #include "airice.h"
 #include "airice_host.h"
+#include "airice_icepath.hpp"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
 #include "airice_icetab.hpp"
@@ -296,6 +297,40 @@ using namespace airice;
 extern "C" {
 
 const char* airice_last_error(void) { return g_err; }
+
+// One in-ice ray's path on the calling thread: the lane functions of icepath_consts_kernel and
+// icepath_kernel (airice_icepath.hpp compiled for the host).
+int airice_icepath_one_host(const double* model3, int kind, double z0, double x1, double z1,
+                            double L, double zmax, double* x, double* z, size_t cap,
+                            int64_t* count) {
+  if (count == nullptr) {
+    set_error("icepath one: null argument (count)");
+    return AIRICE_EINVAL;
+  }
+  int r = -1;
+  for (int k = 0; k < icepath::kKinds; ++k)
+    if (kind == (1 << k)) r = k;
+  if (r < 0) {
+    set_error("icepath one: kind = %d is not one of AIRICE_ICERAY_D, _R, _RA0, _RA1", kind);
+    return AIRICE_EINVAL;
+  }
+  const iceray::IceModel m = model3 != nullptr
+                                 ? iceray::IceModel{model3[0], model3[1], model3[2]}
+                                 : iceray::kDefaultModel;
+  const icepath::Segment s = icepath::make_segment(m, r, z0, x1, z1, L, zmax);
+  *count = s.count;
+  if (s.count == 0) return AIRICE_OK;
+  if (x == nullptr || z == nullptr) {
+    set_error("icepath one: null argument (%s)", x == nullptr ? "x" : "z");
+    return AIRICE_EINVAL;
+  }
+  if ((unsigned long long)s.count > cap) {
+    set_error("icepath one: cap of %zu samples, the ray has %lld", cap, (long long)s.count);
+    return AIRICE_EINVAL;
+  }
+  for (long long k = 0; k < s.count; ++k) icepath::sample(m, s, k, x[k], z[k]);
+  return AIRICE_OK;
+}
 const char* airice_version(void) { return "airice-mi355x 0.2.0 (gfx950, fp64; lookup pack format 2)"; }
 
 int airice_atmosphere_parse(const char* text, size_t len, int variant, airice_medium* out) {

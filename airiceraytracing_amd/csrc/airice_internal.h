@@ -1,7 +1,8 @@
 // airice_internal.h -- host-side internals shared by the runtime and the launchers.
 //
 // The kernels live in airice_table.hip (forward ray: table, rays), airice_solve.hip (minimizer),
-// airice_lookup.hip (the lookup's pack kernels), airice_path.hip and airice_rtf.hip; each opens
+// airice_lookup.hip (the lookup's pack kernels), airice_path.hip, airice_rtf.hip and the in-ice
+// units (airice_iceray.hip, airice_icesol.hip, airice_icetab.hip, airice_icepath.hip); each opens
 // with its own inventory.
 // Data layout in HBM: structure-of-arrays, column c of item i at out[c*ld + i], so each
 // wave's store of one column is one contiguous 256 B (f32) / 512 B (f64) segment.
@@ -211,6 +212,8 @@ enum KTimerId {
   KT_ICETAB_POINTS,
   KT_ICETAB_PACK,
   KT_ICETAB_LOOKUP,
+  KT_ICEPATH_CONSTS,
+  KT_ICEPATH,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -245,6 +248,8 @@ enum LaunchId {
   LC_ICETAB_POINTS, // icetab_points_kernel (an in-ice table build's positions and header)
   LC_ICETAB_PACK,   // icetab_pack_kernel (one record per position)
   LC_ICETAB_LOOKUP, // icetab_lookup_kernel (the in-ice table read)
+  LC_ICEPATH_CONSTS, // icepath_consts_kernel (an in-ice path batch's per-ray records)
+  LC_ICEPATH,       // icepath_kernel (the in-ice ray-path samples)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

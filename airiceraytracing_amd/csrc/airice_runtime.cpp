@@ -209,7 +209,8 @@ static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kerne
                                                "ray_paths_kernel",  "lookup_multi_kernel",
                                                "air2ice_kernel",    "iceray_kernel",
                                                "icesol_kernel",     "icetab_points_kernel",
-                                               "icetab_pack_kernel", "icetab_lookup_kernel"};
+                                               "icetab_pack_kernel", "icetab_lookup_kernel",
+                                               "icepath_consts_kernel", "icepath_kernel"};
 static_assert(sizeof(kKtNames) / sizeof(kKtNames[0]) == KT_COUNT, "one name per timer");
 
 std::atomic<long long> g_launches[LC_COUNT];
@@ -218,7 +219,8 @@ static const char* const kLcNames[LC_COUNT] = {
     "scalar_solve_kernel", "out_kernel",   "lookup_kernel",     "rtf_kernel",
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
     "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel", "iceray_kernel",
-    "icesol_kernel", "icetab_points_kernel", "icetab_pack_kernel", "icetab_lookup_kernel"};
+    "icesol_kernel", "icetab_points_kernel", "icetab_pack_kernel", "icetab_lookup_kernel",
+    "icepath_consts_kernel", "icepath_kernel"};
 static_assert(sizeof(kLcNames) / sizeof(kLcNames[0]) == LC_COUNT, "one name per counter");
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read

@@ -3,7 +3,9 @@
 // calling thread: IceRayTracing() is the solver's host route (iceray_host_one, the function
 // airice_iceray_host runs for n = 1), the *RayPar functions and the (double, void*) functions are
 // the same header's pieces; GetRayTracingSolutions and GetFocusingFactor are icesol_host_one (the
-// function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's.  No HIP here, so this file also builds into the sanitizer driver
+// function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's; the
+// GetFull*RayPath samplers and PlotAndStoreRays are airice_icepath.hpp (bit for bit
+// airice_icepath_one_host).  No HIP here, so this file also builds into the sanitizer driver
 // (tests/cpp/iceray_driver.cpp, `make iceray_asan`).
 // The interpolation tables (SetNumberOfAntennas, MakeTable, GetInterpolatedValue and their
 // extensions, at the end) keep one image per antenna in host memory and read it on the calling
@@ -20,6 +22,7 @@
 
 #include "IceRayTracing.hh"
 #include "airice_host.h"
+#include "airice_icepath.hpp"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
 #include "airice_icetab.hpp"
@@ -40,6 +43,7 @@ int airice_memcpy_d2h(void *, const void *, size_t) __attribute__((weak));
 namespace ir = airice::iceray;
 namespace is = airice::icesol;
 namespace it = airice::icetab;
+namespace ip = airice::icepath;
 
 namespace IceRayTracing {
 
@@ -193,6 +197,44 @@ double *IceRayTracing(double /*x0*/, double z0, double x1, double z1) {
   double *output = new double[AIRICE_ICERAY_REFERENCE_FIELDS];
   for (int c = 0; c < AIRICE_ICERAY_REFERENCE_FIELDS; c++) output[c] = all[c];
   return output;
+}
+
+// GetFull*RayPath (.cc:1257-1712): the samples of airice_icepath.hpp appended to the caller's
+// vectors (the reference's `using namespace std` vector).
+static void append_path(int kind, double z0, double x1, double z1, double L, double zmax,
+                        std::vector<double> &x, std::vector<double> &z) {
+  const ir::IceModel m = model();
+  const ip::Segment s = ip::make_segment(m, kind, z0, x1, z1, L, zmax);
+  const size_t at = x.size(), zat = z.size();
+  x.resize(at + (size_t)s.count);
+  z.resize(zat + (size_t)s.count);
+  for (long long k = 0; k < s.count; k++) ip::sample(m, s, k, x[at + (size_t)k], z[zat + (size_t)k]);
+}
+void GetFullDirectRayPath(double z0, double x1, double z1, double lvalueD, std::vector<double> &x,
+                          std::vector<double> &z) {
+  append_path(0, z0, x1, z1, lvalueD, 0.0, x, z);
+}
+void GetFullReflectedRayPath(double z0, double x1, double z1, double lvalueR,
+                             std::vector<double> &x, std::vector<double> &z) {
+  append_path(1, z0, x1, z1, lvalueR, 0.0, x, z);
+}
+// raynumber named the reference's (commented-out) text file; both refracted rays sample alike
+void GetFullRefractedRayPath(double z0, double x1, double z1, double zmax, double lvalueRa,
+                             std::vector<double> &x, std::vector<double> &z, int raynumber) {
+  append_path(raynumber == 2 ? 3 : 2, z0, x1, z1, lvalueRa, zmax, x, z);
+}
+// .cc:1715-1743: the three under its conditions; the vectors are locals there too
+void PlotAndStoreRays(double /*x0*/, double z0, double z1, double x1, double zmax[2],
+                      double lvalues[4], double checkzeroes[4]) {
+  std::vector<double> xD, zD, xR, zR, xRa[2], zRa[2];
+  GetFullDirectRayPath(z0, x1, z1, lvalues[0], xD, zD);
+  GetFullReflectedRayPath(z0, x1, z1, lvalues[1], xR, zR);
+  if ((std::fabs(checkzeroes[1]) > 0.5 || std::fabs(checkzeroes[0]) > 0.5) &&
+      std::fabs(checkzeroes[2]) < 0.5) {
+    GetFullRefractedRayPath(z0, x1, z1, zmax[0], lvalues[2], xRa[0], zRa[0], 1);
+    if (std::fabs(checkzeroes[3]) < 0.5)
+      GetFullRefractedRayPath(z0, x1, z1, zmax[1], lvalues[3], xRa[1], zRa[1], 2);
+  }
 }
 
 double GetIceTemperature(double z) { return is::ice_temperature(z); }

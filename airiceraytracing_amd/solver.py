@@ -649,6 +649,100 @@ class AirIceSolver:
                                        ptr(st)), "airice_iceray_host")
         return out, st
 
+    # ------------------------------------------------------------------ in-ice ray paths, batched
+    @staticmethod
+    def _ice_ray_paths_plan(z0, z1, status, rays: int):
+        a, b = [np.ascontiguousarray(v).ravel() for v in np.broadcast_arrays(
+            np.asarray(z0, dtype=np.float64), np.asarray(z1, dtype=np.float64))]
+        st = None if status is None else np.ascontiguousarray(status, dtype=np.uint8).ravel()
+        if st is not None and st.size != a.size:
+            raise ValueError(f"ice ray paths: {a.size} pairs, {st.size} status bytes")
+        offsets = np.zeros(4 * a.size + 1, dtype=np.int64)
+        work = ctypes.c_size_t(0)
+        check(lib().airice_icepath_plan(ptr(a), ptr(b), ptr(st), a.size, int(rays), ptr(offsets),
+                                        ctypes.byref(work)), "airice_icepath_plan")
+        return a, b, st, offsets, int(work.value)
+
+    def ice_ray_paths_plan(self, z0, z1, status=None, rays: int = 15) -> np.ndarray:
+        """airice_icepath_plan (host only): the int64 slot offsets of the ray paths of n pairs;
+        segment 4 i + r (r = 0 direct, 1 reflected, 2-3 refracted, of pair i) owns slots
+        [offsets[4i+r], offsets[4i+r+1]) of x and z.  Exact counts for the direct and reflected
+        rays, an upper bound for the refracted ones; 0 for kinds outside ``rays`` (a mask of
+        _lib.ICERAY_D / _R / _RA0 / _RA1) and, with ``status`` (the solver's bytes), for rays the
+        solver did not accept."""
+        return self._ice_ray_paths_plan(z0, z1, status, rays)[3]
+
+    def ice_ray_paths_work_bytes(self, z0, z1, status=None, rays: int = 15) -> int:
+        """Bytes of the device workspace ``ice_ray_paths_device`` needs for this batch."""
+        return self._ice_ray_paths_plan(z0, z1, status, rays)[4]
+
+    def ice_ray_paths_device(self, z0, x1, z1, rays_out, offsets, count, x, z, z0_host=None,
+                             z1_host=None, status=None, rays: int = 15, work=None, stream=None,
+                             model=None):
+        """airice_icepath_launch: the x(z) samples of every accepted ray of n pairs, over
+        ``rays_out``, the (32, ld) tensor ``ice_rays_device`` wrote for the same ``z0``, ``x1``,
+        ``z1`` (n float64 device tensors each).  ``count`` (4n int64), ``x`` and ``z``
+        (>= offsets[4n] float64 each) are device tensors; ``offsets`` (from
+        ``ice_ray_paths_plan``), ``z0_host`` / ``z1_host`` (the depths the plan was made from;
+        copied back from the device, which synchronises, when not given) and ``status`` stay on
+        the host.  ``work`` is a device byte tensor of ``ice_ray_paths_work_bytes``; without one it
+        is allocated here.  Stream-ordered; returns the workspace, which must outlive the launch.
+        Slots past a segment's count keep what they held."""
+        import torch
+        n = int(z0.numel())
+        a = z0.detach().cpu().numpy() if z0_host is None else z0_host
+        b = z1.detach().cpu().numpy() if z1_host is None else z1_host
+        a, b, st, planned, need = self._ice_ray_paths_plan(a, b, status, rays)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        if a.size != n or off.size != 4 * n + 1:
+            raise ValueError(f"ice_ray_paths_device: {n} pairs, {a.size} host depths, "
+                             f"{off.size} offsets")
+        if work is None:
+            work = torch.empty(max(need, 16), dtype=torch.uint8, device=z0.device)
+        m = self._ice_model(model)
+        check(lib().airice_icepath_launch(
+            ptr(m), ptr(z0), ptr(x1), ptr(z1), ptr(rays_out), int(rays_out.stride(0)), ptr(a),
+            ptr(b), ptr(st), n, int(rays), ptr(off), ptr(work), int(work.numel()), ptr(count),
+            ptr(x), ptr(z), min(int(x.numel()), int(z.numel())), _stream_handle(stream)),
+            "airice_icepath_launch")
+        return work
+
+    def ice_ray_paths_host(self, z0, x1, z1, model=None, rays: int = 15):
+        """Solver, plan and paths in one call (numpy in, numpy out): ``ice_rays_host``, then the
+        paths of every ray it accepted.  Returns (offsets (4n+1), count (4n), x, z): segment
+        s = 4 i + r holds its count[s] samples at x / z[offsets[s] : offsets[s] + count[s]], in
+        the reference's order (from the upper of the two depths, over the surface or the turning
+        depth, down to the lower).  One pair in SCALAR_HOST mode runs on the calling thread
+        (airice_icepath_one_host); otherwise the batch is copied to the GPU, sampled in two
+        launches and copied back."""
+        arrs = np.broadcast_arrays(*[np.asarray(v, dtype=np.float64) for v in (z0, x1, z1)])
+        a, b, c = [np.ascontiguousarray(v).ravel() for v in arrs]
+        n = a.size
+        out, st = self.ice_rays_host(a, b, c, model=model)
+        _, _, _, offsets, _ = self._ice_ray_paths_plan(a, c, st, rays)
+        total = int(offsets[-1])
+        count = np.zeros(4 * n, dtype=np.int64)
+        x = np.full(total, np.nan)
+        z = np.full(total, np.nan)
+        m = self._ice_model(model)
+        if n == 1 and lib().airice_scalar_mode(-1) == _lib.SCALAR_HOST:
+            for r in range(4):
+                cap = int(offsets[r + 1] - offsets[r])
+                if cap == 0:
+                    continue
+                cnt = ctypes.c_int64(0)
+                lo = int(offsets[r])
+                check(lib().airice_icepath_one_host(
+                    ptr(m), 1 << r, a[0], b[0], c[0], out[_lib.ICERAY_LVALUE + r, 0],
+                    out[_lib.ICERAY_ZMAX + r - 2, 0] if r >= 2 else 0.0, ptr(x[lo:]), ptr(z[lo:]),
+                    cap, ctypes.byref(cnt)), "airice_icepath_one_host")
+                count[r] = cnt.value
+        elif n > 0:
+            check(lib().airice_icepath_host(ptr(m), ptr(a), ptr(b), ptr(c), ptr(out), max(n, 1),
+                                            ptr(st), n, int(rays), ptr(offsets), ptr(count),
+                                            ptr(x), ptr(z), total), "airice_icepath_host")
+        return offsets, count, x, z
+
     def ice_solutions_device(self, z0, x1, z1, rays, out, status=None, a0: float = 1.0,
                              frequency: float = 0.1, rays_lower=None, ld: int | None = None,
                              stream=None, model=None) -> None:

@@ -39,13 +39,24 @@
  *     doubles (the reference narrows GridPositionXb / GridPositionZb to float).  MakeTables,
  *     GetInterpolatedValues, GetInterpolatedValuesBatch and SetTable are extensions.  The table
  *     state is shared and, like the reference's, not reentrant.
- * Not provided: the _Cnz and _Air variants, DirectRayTracer, the GetFull*RayPath samplers, and
- * FindFunctionRoot* with GSL-typed arguments.
+ *   - GetFullDirectRayPath, GetFullReflectedRayPath and GetFullRefractedRayPath append a ray's
+ *     x(z) samples (0.5 m depth steps, the reference's order) to the caller's vectors, on the
+ *     calling thread (bit for bit airice_icepath_one_host; batches: airice_icepath_launch).
+ *     Differences: a downward leg's depth is start - 0.5 k rounded once, where the
+ *     reference chains zn = zn - h (the same counts, depths within 1 ulp); no sample is dropped
+ *     (n^2 - L^2 is clamped at 0 where the reference skips a NaN); on a refracted ray n(z) - L is
+ *     formed about the turning depth of L without cancellation; nothing is appended for a
+ *     non-finite argument or a depth above 0 or below -50,000 m.  PlotAndStoreRays calls the three
+ *     under the reference's conditions and, like it, discards the vectors.
+ * Not provided: the _Cnz and _Air variants, DirectRayTracer, and FindFunctionRoot* with GSL-typed
+ * arguments.
  * Link: -L<repo>/airiceraytracing_amd -lairice. */
 #ifndef AIRICE_ICERAYTRACING_HH_
 #define AIRICE_ICERAYTRACING_HH_
 
 #include <stddef.h>
+
+#include <vector>
 
 #include "airice.h"
 
@@ -95,6 +106,16 @@ double *GetReflectedRayPar(double z0, double x1, double z1);
 double *GetRefractedRayPar(double z0, double x1, double z1, double LangR, double RangR,
                            double checkzeroD, double checkzeroR);
 double *IceRayTracing(double x0, double z0, double x1, double z1);
+
+/* The sampled ray paths (.cc:1257-1743): x and z are appended to */
+void GetFullDirectRayPath(double z0, double x1, double z1, double lvalueD, std::vector<double> &x,
+                          std::vector<double> &z);
+void GetFullReflectedRayPath(double z0, double x1, double z1, double lvalueR,
+                             std::vector<double> &x, std::vector<double> &z);
+void GetFullRefractedRayPath(double z0, double x1, double z1, double zmax, double lvalueRa,
+                             std::vector<double> &x, std::vector<double> &z, int raynumber);
+void PlotAndStoreRays(double x0, double z0, double z1, double x1, double zmax[2],
+                      double lvalues[4], double checkzeroes[4]);
 
 /* Ice temperature (C) and attenuation length (m) at depth z, frequency in GHz (.cc:134-163) */
 double GetIceTemperature(double z);

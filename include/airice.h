@@ -642,6 +642,64 @@ int airice_icetab_lookup_host(const double *h_image, size_t n_ant, const int32_t
                               const double *x, const double *z, size_t n, double *out, size_t ld,
                               uint8_t *status);
 
+/* --- in-ice ray paths (IceRayTracing::GetFullDirectRayPath / GetFullReflectedRayPath /
+ * GetFullRefractedRayPath, IceRayTracing.cc:1257-1712) -------------------------------------------
+ * The x(z) polyline of every accepted ray of n pairs, over the rows airice_iceray_launch wrote, in
+ * two launches: icepath_consts_kernel (one lane per (pair, kind) segment) and icepath_kernel (one
+ * lane per sample).  One ray is (kind, z0, x1, z1, L, zmax), kind one of AIRICE_ICERAY_D / _R /
+ * _RA0 / _RA1, zmax read by the refracted kinds only.  With the reference's flip applied (z0 > z1
+ * swaps them and emits x1 - xn), h = 0.5 m and F(z) = fDnfR(z; A, B, +C, L), in its order:
+ *   D   zn = z1 - 0.5 k while zn >= z0, xn = F(zn) - F(z0); then the closing sample at z0 (z0
+ *       appears twice when z1 - z0 is a multiple of 0.5);
+ *   R   zn = z1 + 0.5 k while zn <= 0, xn = 2 F(-1e-7) - F(zn) - F(z0); zn = -1e-7 - 0.5 k while
+ *       zn >= z0, xn = F(zn) - F(z0); then the closing sample;
+ *   Ra  as R with -zmax for the surface: leg 1 while zn <= -zmax, leg 2 from -zmax.
+ * Departures: a downward leg's depth is start - 0.5 k rounded once (the reference
+ * chains zn = zn - h: the same counts, depths within 1 ulp); no sample is dropped (n^2 - L^2 is
+ * clamped at 0 where the reference skips a NaN), so a count depends on (z0, z1, zmax) alone; on a
+ * refracted ray n(z) - L = (L - A) expm1(-C (|z| - zt)), zt the turning depth of L, without
+ * cancellation.  A ray whose status bit is clear, an AIRICE_ICERAY_NONFINITE row and a pair with a
+ * depth above 0 or below -50,000 m (the reference's 100,000 steps) have count 0.
+ *
+ * Segment s = 4 i + r (r = 0 D, 1 R, 2 Ra0, 3 Ra1 of pair i) owns slots [offsets[s], offsets[s+1])
+ * of x and z and fills the first count[s] of them; the rest are left untouched.
+ *
+ * Plan (host only, no GPU needed): offsets[0 .. 4n], offsets[0] = 0.  Capacities: the exact count
+ * for D and R (they depend on the depths alone); for Ra the reflected count + 1, which bounds it
+ * for every zmax >= 0, so the launch needs no copy back of zmax and stays stream-ordered behind
+ * the solver; 0 for a kind outside ray_mask (AIRICE_ICERAY_* bits), for a kind whose bit is clear
+ * in status[i] (status nullable: every kind) and for the pairs above.  *work_bytes (nullable): the
+ * size of the launch's workspace. */
+int airice_icepath_plan(const double *z0 /* host */, const double *z1 /* host */,
+                        const uint8_t *status /* host, nullable */, size_t n, int ray_mask,
+                        int64_t *offsets /* host, 4n+1 */, size_t *work_bytes);
+/* Stream-ordered, no device allocation, exactly the two kernels after the upload of the plan into
+ * d_work (work_bytes device bytes, 16-byte aligned).  d_z0 / d_x1 / d_z1: n device doubles;
+ * d_rays: the solver's 32 columns of stride ld_rays (columns 19-24 and 29 are read; a segment
+ * whose bit is clear there, or whose count exceeds its capacity, has count 0); z0 / z1 / status /
+ * offsets: host, as given to / filled by the plan (checked against it); d_count: 4n device int64;
+ * d_x / d_z: cap >= offsets[4n] doubles each.  n == 0 or a plan of no samples is AIRICE_OK and
+ * launches nothing (d_count is then not written); a null required pointer, ld_rays < n, a cap or
+ * work_bytes that is too small, or offsets that are not the plan's is AIRICE_EINVAL before any
+ * device call, and airice_last_error() names the argument. */
+int airice_icepath_launch(const double *model3, const double *d_z0, const double *d_x1,
+                          const double *d_z1, const double *d_rays, size_t ld_rays,
+                          const double *z0, const double *z1, const uint8_t *status, size_t n,
+                          int ray_mask, const int64_t *offsets, void *d_work, size_t work_bytes,
+                          int64_t *d_count, double *d_x, double *d_z, size_t cap, void *stream);
+/* The same with every array on the host (rays: the 32 columns airice_iceray_host returned): copies,
+ * launches and synchronises. */
+int airice_icepath_host(const double *model3, const double *z0, const double *x1, const double *z1,
+                        const double *rays, size_t ld_rays, const uint8_t *status, size_t n,
+                        int ray_mask, const int64_t *offsets, int64_t *count, double *x, double *z,
+                        size_t cap);
+/* One ray on the calling thread, from the source the kernels are compiled from; no GPU (the
+ * engine of the drop-in's GetFull*RayPath).  kind: one AIRICE_ICERAY_* ray bit.  *count = the
+ * ray's samples; x / z (cap doubles each) receive them; a cap below the count is AIRICE_EINVAL. */
+int airice_icepath_one_host(const double *model3, int kind, double z0, double x1, double z1,
+                            double L, double zmax, double *x, double *z, size_t cap,
+                            int64_t *count);
+
 /* Device bookkeeping (thin wrappers so ctypes callers need no HIP runtime binding). */
 int airice_device_count(int *count);
 int airice_set_device(int device);
@@ -697,7 +755,8 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * kernels of airice_ray_paths_launch), "air2ice_kernel" (airice_air2ice_launch), "iceray_kernel"
  * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
  * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
- * (airice_icetab_lookup_launch).
+ * (airice_icetab_lookup_launch), "icepath_consts_kernel" and "icepath_kernel" (the two kernels of
+ * airice_icepath_launch).
  * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -715,7 +774,8 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * table launch's air record, below; it does not count as "table_kernel"), "iceray_kernel"
  * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
  * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
- * (airice_icetab_lookup_launch).
+ * (airice_icetab_lookup_launch), "icepath_consts_kernel", "icepath_kernel"
+ * (airice_icepath_launch).
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
