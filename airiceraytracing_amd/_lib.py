@@ -209,6 +209,7 @@ EXPORTED_SYMBOLS = (
     "airice_trace_ice_to_air_host", "airice_rtf_outputs", "airice_rtf_eval",
     "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host",
     "airice_iceray_launch", "airice_iceray_host", "airice_icesol_launch", "airice_icesol_host",
+    "airice_icesol_spectrum_launch", "airice_icesol_spectrum_host",
     "airice_icetab_grid_init", "airice_icetab_grid", "airice_icetab_layout",
     "airice_icetab_pack_host", "airice_icetab_work_bytes", "airice_icetab_build_launch",
     "airice_icetab_build_host", "airice_icetab_lookup_launch", "airice_icetab_lookup_host",
@@ -298,6 +299,8 @@ def lib() -> ctypes.CDLL:
         "airice_iceray_host": ([P, P, P, P, S, P, S, P], I),
         "airice_icesol_launch": ([P, P, P, P, P, S, P, S, S, D, D, P, S, P, P], I),
         "airice_icesol_host": ([P, P, P, P, S, D, D, I, P, S, P], I),
+        "airice_icesol_spectrum_launch": ([P, P, P, P, S, P, S, S, D, P, S, P, S, P], I),
+        "airice_icesol_spectrum_host": ([P, P, P, P, S, D, P, S, P, S, P, P, S], I),
         "airice_icetab_grid_init": ([D, D, D, P], I),
         "airice_icetab_grid": ([D, D, D, D, ctypes.c_int32, ctypes.c_int32, D, P], I),
         "airice_icetab_layout": ([P, S, ctypes.POINTER(S)], I),

@@ -15,6 +15,7 @@
 #include "airice_icepath.hpp"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
+#include "airice_icespec.hpp"
 #include "airice_icetab.hpp"
 
 namespace airice {
@@ -288,6 +289,26 @@ const char* icesol_bad_value(const double model[3], double a0, double frequency_
   if (!(model[1] < 0 && model[2] > 0 && iceray::is_finite(model[1]) && iceray::is_finite(model[2])))
     return "model3 is outside B < 0 < C";
   return nullptr;
+}
+
+void icespec_host_one(const double model[3], const double in[3], double a0,
+                      const double* frequency_ghz, size_t n_freq, double* out18, uint8_t* status,
+                      double* att0, double* att1) {
+  const iceray::IceModel m = {model[0], model[1], model[2]};
+  const icesol::Medium q = icesol::make_medium(a0, frequency_ghz[0]);
+  double at[iceray::kColumns];
+  iceray::solve_pair(m, in[0], in[1], in[2], iceray::ArrayOut{at});
+  const auto ray = [&](int c) { return at[c]; };
+  const uint8_t st = icesol::solve_pair(m, q, in[0], in[1], in[2], ray, false, ray,
+                                        icesol::ArrayOut{out18});
+  if (status != nullptr) *status = st;
+  icespec::spectrum_pair(m, a0, in[0], in[2], ray, out18[icesol::kColType],
+                         out18[icesol::kColType + 1], frequency_ghz, n_freq, att0, att1);
+}
+
+// the frequencies are per bin and none is refused, so any valid one stands in for them here
+const char* icespec_bad_value(const double model[3], double a0) {
+  return icesol_bad_value(model, a0, 1.0);
 }
 
 }  // namespace airice

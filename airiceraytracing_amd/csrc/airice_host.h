@@ -29,5 +29,13 @@ void icesol_host_one(const double model[3], const double in[3], double a0, doubl
 // The argument checks the icesol entries share: nullptr, or what is wrong with a0, the frequency
 // or the model (a static string for airice_last_error()).
 const char* icesol_bad_value(const double model[3], double a0, double frequency_ghz);
+// The same pair's solutions without focusing at frequency[0], then the attenuation of its two rays
+// at each of the n_freq frequencies (airice_icespec.hpp compiled for the host): att0 / att1 = slot
+// 0 / 1, n_freq values each.  No frequency is refused: a bad one makes its bin NaN.
+void icespec_host_one(const double model[3], const double in[3], double a0,
+                      const double* frequency_ghz, size_t n_freq, double* out18, uint8_t* status,
+                      double* att0, double* att1);
+// The value checks the spectrum entries share: a0 and the model, as icesol_bad_value.
+const char* icespec_bad_value(const double model[3], double a0);
 
 }  // namespace airice

@@ -2,8 +2,8 @@
 //
 // The kernels live in airice_table.hip (forward ray: table, rays), airice_solve.hip (minimizer),
 // airice_lookup.hip (the lookup's pack kernels), airice_path.hip, airice_rtf.hip and the in-ice
-// units (airice_iceray.hip, airice_icesol.hip, airice_icetab.hip, airice_icepath.hip); each opens
-// with its own inventory.
+// units (airice_iceray.hip, airice_icesol.hip, airice_icespec.hip, airice_icetab.hip,
+// airice_icepath.hip); each opens with its own inventory.
 // Data layout in HBM: structure-of-arrays, column c of item i at out[c*ld + i], so each
 // wave's store of one column is one contiguous 256 B (f32) / 512 B (f64) segment.
 #pragma once
@@ -139,6 +139,15 @@ int launch_icesol(const double model[3], double a0, double frequency_ghz, const 
                   const double* x1, const double* z1, const double* rays, size_t ld_rays,
                   const double* rays_lower, size_t ld_lower, size_t n, double* out, size_t ld,
                   uint8_t* status, hipStream_t st);
+// The two chosen rays' attenuation at n_freq frequencies (airice_icespec.hip):
+// icesol_spectrum_kernel, icespec_pairs_per_block(n_freq) pairs per block, over the solver's rows
+// and the type columns of launch_icesol's output; att[(2 i + slot) ld_f + k].  The pair's function
+// on the calling thread is icespec_host_one (airice_host.h).
+AIRICE_LOCAL unsigned icespec_pairs_per_block(size_t n_freq);
+AIRICE_LOCAL int launch_icespec(const double model[3], double a0, const double* z0,
+                                const double* z1, const double* rays, size_t ld_rays,
+                                const double* sol, size_t ld_sol, size_t n, const double* freq,
+                                size_t n_freq, double* att, size_t ld_f, hipStream_t st);
 
 static_assert(kMaxParsedLayers == kMaxLayers, "parse and kernels agree on the layer count");
 
@@ -214,6 +223,7 @@ enum KTimerId {
   KT_ICETAB_LOOKUP,
   KT_ICEPATH_CONSTS,
   KT_ICEPATH,
+  KT_ICESPEC,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -250,6 +260,7 @@ enum LaunchId {
   LC_ICETAB_LOOKUP, // icetab_lookup_kernel (the in-ice table read)
   LC_ICEPATH_CONSTS, // icepath_consts_kernel (an in-ice path batch's per-ray records)
   LC_ICEPATH,       // icepath_kernel (the in-ice ray-path samples)
+  LC_ICESPEC,       // icesol_spectrum_kernel (the two rays' attenuation over a frequency grid)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

@@ -210,7 +210,8 @@ static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kerne
                                                "air2ice_kernel",    "iceray_kernel",
                                                "icesol_kernel",     "icetab_points_kernel",
                                                "icetab_pack_kernel", "icetab_lookup_kernel",
-                                               "icepath_consts_kernel", "icepath_kernel"};
+                                               "icepath_consts_kernel", "icepath_kernel",
+                                               "icesol_spectrum_kernel"};
 static_assert(sizeof(kKtNames) / sizeof(kKtNames[0]) == KT_COUNT, "one name per timer");
 
 std::atomic<long long> g_launches[LC_COUNT];
@@ -220,7 +221,7 @@ static const char* const kLcNames[LC_COUNT] = {
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
     "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel", "iceray_kernel",
     "icesol_kernel", "icetab_points_kernel", "icetab_pack_kernel", "icetab_lookup_kernel",
-    "icepath_consts_kernel", "icepath_kernel"};
+    "icepath_consts_kernel", "icepath_kernel", "icesol_spectrum_kernel"};
 static_assert(sizeof(kLcNames) / sizeof(kLcNames[0]) == LC_COUNT, "one name per counter");
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
@@ -1055,6 +1056,93 @@ int airice_icesol_host(const double* model3, const double* z0, const double* x1,
                                               focus ? s.col(3) : nullptr, s.scratch, n, a0,
                                               frequency_ghz, s.out, s.status, nullptr);
                      });
+}
+
+// ---- the two rays' attenuation over a frequency grid ---------------------------------------------
+// What is wrong with the values and sizes of a spectrum call (set as the error), or AIRICE_OK.
+static int icespec_refuses(const double* model3, double a0, size_t n_freq, size_t ld_f) {
+  if (n_freq == 0) {
+    set_error("icespec: n_freq is 0");
+    return AIRICE_EINVAL;
+  }
+  if (int rc = short_stride("icespec", "ld_f", ld_f, n_freq)) return rc;
+  if (n_freq > ((size_t)1 << 27)) {  // 16 pairs x n_freq items in 32 bits
+    set_error("icespec: n_freq = %zu exceeds one launch", n_freq);
+    return AIRICE_EINVAL;
+  }
+  if (const char* bad = airice::icespec_bad_value(ice_model_or_default(model3), a0)) {
+    set_error("icespec: %s", bad);
+    return AIRICE_EINVAL;
+  }
+  return AIRICE_OK;
+}
+
+int airice_icesol_spectrum_launch(const double* model3, const double* d_z0, const double* d_z1,
+                                  const double* d_rays, size_t ld_rays, const double* d_sol,
+                                  size_t ld_sol, size_t n, double a0, const double* d_freq_ghz,
+                                  size_t n_freq, double* d_att, size_t ld_f, void* stream) {
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("icespec", {{"z0", d_z0}, {"z1", d_z1}, {"rays", d_rays},
+                                         {"sol", d_sol}, {"freq_ghz", d_freq_ghz},
+                                         {"att", d_att}}))
+    return rc;
+  if (int rc = icespec_refuses(model3, a0, n_freq, ld_f)) return rc;
+  if (int rc = short_stride("icespec", "ld_rays", ld_rays, n)) return rc;
+  if (int rc = short_stride("icespec", "ld_sol", ld_sol, n)) return rc;
+  if (int rc = exceeds_one_launch("icespec", n, airice::icespec_pairs_per_block(n_freq)))
+    return rc;
+  return airice::launch_icespec(ice_model_or_default(model3), a0, d_z0, d_z1, d_rays, ld_rays,
+                                d_sol, ld_sol, n, d_freq_ghz, n_freq, d_att, ld_f,
+                                (hipStream_t)stream);
+}
+
+int airice_icesol_spectrum_host(const double* model3, const double* z0, const double* x1,
+                                const double* z1, size_t n, double a0, const double* freq_ghz,
+                                size_t n_freq, double* sol_out, size_t ld, uint8_t* status,
+                                double* att_out, size_t ld_f) {
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("icespec", {{"z0", z0}, {"x1", x1}, {"z1", z1},
+                                         {"freq_ghz", freq_ghz}, {"sol_out", sol_out},
+                                         {"att_out", att_out}}))
+    return rc;
+  if (int rc = icespec_refuses(model3, a0, n_freq, ld_f)) return rc;
+  if (int rc = short_stride("icespec", "ld", ld, n)) return rc;
+  constexpr int kF = AIRICE_ICESOL_FIELDS, kR = AIRICE_ICERAY_FIELDS;
+  if (n == 1 && airice::scalar_on_host()) {  // one pair on the calling thread
+    const double in[3] = {z0[0], x1[0], z1[0]};
+    double o[kF];
+    uint8_t st = 0;
+    airice::icespec_host_one(ice_model_or_default(model3), in, a0, freq_ghz, n_freq, o, &st,
+                             att_out, att_out + ld_f);
+    scatter_one(o, kF, st, sol_out, ld, status);
+    return AIRICE_OK;
+  }
+  // The staged block's scratch: the solver's rows, the frequencies, the spectra.  The solutions
+  // are at freq_ghz[0], which -- like every bin -- is not refused: a bad one gives NaN columns.
+  if (int rc = exceeds_one_launch("icespec", n)) return rc;
+  const size_t n_rays = (size_t)kR * n, n_att = 2 * n * n_freq;
+  const double* cols[3] = {z0, x1, z1};
+  return staged_call(cols, 3, n, n_rays + n_freq + n_att, kF, sol_out, ld, status,
+                     [&](const Staged& s) -> int {
+    double* rays = s.scratch;
+    double* freq = rays + n_rays;
+    double* att = freq + n_freq;
+    HIP_TRY(hipMemcpy(freq, freq_ghz, sizeof(double) * n_freq, hipMemcpyHostToDevice));
+    int rc = airice_iceray_launch(model3, s.col(0), s.col(1), s.col(2), n, rays, n, nullptr,
+                                  nullptr);
+    if (rc == AIRICE_OK)
+      rc = airice::launch_icesol(ice_model_or_default(model3), a0, freq_ghz[0], s.col(0),
+                                 s.col(1), s.col(2), rays, n, nullptr, 0, n, s.out, n, s.status,
+                                 nullptr);
+    if (rc == AIRICE_OK)
+      rc = airice_icesol_spectrum_launch(model3, s.col(0), s.col(2), rays, n, s.out, n, n, a0,
+                                         freq, n_freq, att, n_freq, nullptr);
+    if (rc) return rc;
+    // the copy waits for the kernels: the call's one synchronisation
+    HIP_TRY(hipMemcpy2D(att_out, sizeof(double) * ld_f, att, sizeof(double) * n_freq,
+                        sizeof(double) * n_freq, 2 * n, hipMemcpyDeviceToHost));
+    return AIRICE_OK;
+  });
 }
 
 int airice_single_ray_host(const airice_medium* m, double antenna_depth_m, double launch_deg,

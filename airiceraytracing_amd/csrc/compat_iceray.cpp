@@ -3,7 +3,8 @@
 // calling thread: IceRayTracing() is the solver's host route (iceray_host_one, the function
 // airice_iceray_host runs for n = 1), the *RayPar functions and the (double, void*) functions are
 // the same header's pieces; GetRayTracingSolutions and GetFocusingFactor are icesol_host_one (the
-// function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's; the
+// function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's,
+// GetAttenuationSpectrum icespec_host_one (airice_icespec.hpp); the
 // GetFull*RayPath samplers and PlotAndStoreRays are airice_icepath.hpp (bit for bit
 // airice_icepath_one_host).  No HIP here, so this file also builds into the sanitizer driver
 // (tests/cpp/iceray_driver.cpp, `make iceray_asan`).
@@ -296,6 +297,25 @@ void GetFocusingFactor(double zT, double xR, double zR, double focusing[2]) {
   if (st & AIRICE_ICESOL_FOCUS0) focusing[0] = o[AIRICE_ICESOL_FOCUSING];
   if (st & AIRICE_ICESOL_FOCUS1) focusing[1] = o[AIRICE_ICESOL_FOCUSING + 1];
   if (zR == zT && focusing[0] == 0) focusing[0] = 1.;
+}
+
+// Extension: AttRay of the same two rays at n_freq frequencies, on the calling thread -- the
+// function airice_icesol_spectrum_host runs for n = 1 (airice_icespec.hpp)
+int GetAttenuationSpectrum(double RxDepth, double Distance, double TxDepth, double A0,
+                           const double *frequency, size_t n_freq, double *AttRay0,
+                           double *AttRay1) {
+  const double m[3] = {A_ice, B_ice, C_ice};
+  const char *bad = frequency == nullptr || AttRay0 == nullptr || AttRay1 == nullptr
+                        ? "null argument"
+                        : n_freq == 0 ? "n_freq is 0" : airice::icespec_bad_value(m, A0);
+  if (bad != nullptr) {
+    airice::set_error("GetAttenuationSpectrum: %s", bad);
+    return AIRICE_EINVAL;
+  }
+  const double in[3] = {TxDepth, Distance, RxDepth};
+  double o[AIRICE_ICESOL_FIELDS];
+  airice::icespec_host_one(m, in, A0, frequency, n_freq, o, nullptr, AttRay0, AttRay1);
+  return AIRICE_OK;
 }
 
 // ---- interpolation tables (.cc:2614-2905, 3212-3216) -------------------------------------------

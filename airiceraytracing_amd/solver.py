@@ -778,6 +778,43 @@ class AirIceSolver:
                                        max(n, 1), ptr(st)), "airice_icesol_host")
         return out, st
 
+    def ice_attenuation_spectrum_device(self, z0, z1, rays, sol, freq, out, a0: float = 1.0,
+                                        ld_f: int | None = None, stream=None, model=None) -> None:
+        """airice_icesol_spectrum_launch: the ice attenuation of each pair's two rays at every
+        frequency of ``freq`` (F float64 GHz, a device tensor) in one launch, over ``rays`` (what
+        ``ice_rays_device`` wrote) and ``sol`` (what ``ice_solutions_device`` wrote for the same
+        pairs at any frequency: only its two ray-type rows are read).  ``out`` is a device tensor
+        of 2 n rows of ``ld_f`` (default F) float64: AttRay of pair i, slot s, bin k at
+        ``out.view(-1)[(2 i + s) ld_f + k]``, i.e. an (n, 2, F) tensor when ld_f == F.  A bin
+        whose frequency is not finite and positive is NaN where the slot holds a ray.
+        Stream-ordered."""
+        n, f = int(z0.numel()), int(freq.numel())
+        m = self._ice_model(model)
+        check(lib().airice_icesol_spectrum_launch(
+            ptr(m), ptr(z0), ptr(z1), ptr(rays), int(rays.stride(0)), ptr(sol),
+            int(sol.stride(0)), n, float(a0), ptr(freq), f, ptr(out), f if ld_f is None else ld_f,
+            _stream_handle(stream)), "airice_icesol_spectrum_launch")
+
+    def ice_attenuation_spectrum_host(self, z0, x1, z1, freq, a0: float = 1.0, model=None):
+        """airice_icesol_spectrum_host: numpy in, numpy out; the three inputs broadcast against
+        each other, ``freq`` is the list of F frequencies (GHz).  Returns (sol (18, n) -- the
+        solutions without focusing at freq[0] --, status (n) uint8, att (n, 2, F)).  One pair
+        runs where scalar_mode() says (the calling thread by default); more are copied to the
+        GPU, solved (iceray_kernel, icesol_kernel and icesol_spectrum_kernel once each) and copied
+        back."""
+        arrs = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in (z0, x1, z1)])
+        a, b, c = [np.ascontiguousarray(v).ravel() for v in arrs]
+        fr = np.ascontiguousarray(freq, dtype=np.float64).ravel()
+        n, f = a.size, fr.size
+        sol = np.empty((_lib.ICESOL_FIELDS, n), dtype=np.float64)
+        st = np.empty(n, dtype=np.uint8)
+        att = np.empty((n, 2, f), dtype=np.float64)
+        m = self._ice_model(model)
+        check(lib().airice_icesol_spectrum_host(ptr(m), ptr(a), ptr(b), ptr(c), n, float(a0),
+                                                ptr(fr), f, ptr(sol), max(n, 1), ptr(st),
+                                                ptr(att), f), "airice_icesol_spectrum_host")
+        return sol, st, att
+
     # ------------------------------------------------------------------ in-ice tables
     def ice_tables(self, shower_hit_distance, shower_depth, rx_depths, a0: float = 1.0,
                    frequency: float = 0.1, model=None, grids=None, stream=None) -> IceTables:

@@ -28,7 +28,8 @@
  *     the turning depth of Lvalue itself and does not read zmax; a limit above the depth where
  *     n = L, or L >= A, gives NaN; GetIceTemperature is the cubic in Horner form.  It needs
  *     B < 0 < C.  A NaN or infinite input of GetRayTracingSolutions gives NaN values with
- *     IgnoreCh 0.
+ *     IgnoreCh 0.  GetAttenuationSpectrum is an extension: the two rays' AttRay over a list of
+ *     frequencies in one call (batches: airice_icesol_spectrum_launch).
  *   - SetNumberOfAntennas, MakeTable and GetInterpolatedValue are the reference's three-call table
  *     workflow.  MakeTable solves its 401 x 201 grid on the GPU in four launches and
  *     keeps the table in host memory; GetInterpolatedValue runs on the calling thread (bit for bit
@@ -182,6 +183,17 @@ inline int GetRayTracingSolutionsBatch(const double *TxDepth, const double *Dist
   return airice_icesol_host(model, TxDepth, Distance, RxDepth, n, A0, frequency, focusing, out,
                             ld, status);
 }
+
+/* AttRay of GetRayTracingSolutions' two rays at each of n_freq frequencies (GHz) on the calling
+ * thread: AttRay0[k] / AttRay1[k] are what GetRayTracingSolutions(RxDepth, Distance, TxDepth, ...,
+ * A0, frequency[k], AttRay) leaves in AttRay[0] / AttRay[1] (within 1e-12; bit for bit
+ * airice_icesol_spectrum_host with n = 1), with the rays found and their nodes formed once, not
+ * once per bin.  A frequency that is not finite and positive gives NaN in its bin.  AIRICE_OK, or
+ * AIRICE_EINVAL (airice_last_error()) for a null pointer, n_freq == 0, a non-finite A0 or a model
+ * outside B < 0 < C. */
+int GetAttenuationSpectrum(double RxDepth, double Distance, double TxDepth, double A0,
+                           const double *frequency, size_t n_freq, double *AttRay0,
+                           double *AttRay1);
 
 }  // namespace IceRayTracing
 

@@ -564,6 +564,40 @@ int airice_icesol_host(const double *model3, const double *z0, const double *x1,
                        size_t n, double a0, double frequency_ghz, int focusing, double *out,
                        size_t ld, uint8_t *status);
 
+/* --- the two rays' ice attenuation over a frequency grid (no reference counterpart: a consumer of
+ * GetRayTracingSolutions calls it once per bin of a pulse's spectrum) -------------------------------
+ * For n pairs x n_freq frequencies in ONE launch of icesol_spectrum_kernel, over d_rays (the rows
+ * airice_iceray_launch wrote, stride ld_rays) and d_sol (what airice_icesol_launch wrote for the
+ * same pairs, stride ld_sol; only its two AIRICE_ICESOL_RAY_TYPE columns are read: the slots hold
+ * the rays it chose, at whatever frequency it ran).  d_freq_ghz: n_freq doubles in device memory.
+ * AttRay of pair i, slot s, bin k lands at d_att[(2*i + s)*ld_f + k]: a pair's spectrum is
+ * contiguous in frequency; the padding [n_freq, ld_f) of a row is left alone.  It is
+ * 1 - |a0 * integral of ds / L_att(z, d_freq_ghz[k])| where the slot holds a ray and 0.0 where it
+ * does not, with airice_icesol_launch's 24-node rule: a node's depth, index, temperature and
+ * weight are formed once per pair, and a bin costs one exp per node.  Against
+ * airice_icesol_launch at the same frequency: within 1e-12 * max(1, |1 - AttRay|), not bit for
+ * bit.  A frequency that is not finite and positive makes its bin NaN where the slot holds a ray
+ * (it is not refused: the frequencies stay on the device); a pair whose solver row is
+ * AIRICE_ICERAY_NONFINITE is NaN in every bin of both slots.
+ * Stream-ordered, no device allocation, no synchronisation, exactly one kernel launch; n == 0 is
+ * AIRICE_OK and nothing is launched.  AIRICE_EINVAL before any device call: a null pointer;
+ * n_freq == 0 (or above 2^27); ld_f < n_freq; ld_rays < n or ld_sol < n; a non-finite a0; a model
+ * outside B < 0 < C. */
+int airice_icesol_spectrum_launch(const double *model3, const double *d_z0, const double *d_z1,
+                                  const double *d_rays, size_t ld_rays, const double *d_sol,
+                                  size_t ld_sol, size_t n, double a0, const double *d_freq_ghz,
+                                  size_t n_freq, double *d_att, size_t ld_f, void *stream);
+/* The whole of it with every array on the host: sol_out (AIRICE_ICESOL_FIELDS columns of stride
+ * ld, without focusing) and status as airice_icesol_host at freq_ghz[0] -- so its two attenuation
+ * columns are bin 0's --, att_out[(2*i + s)*ld_f + k] as above.  n > 1: copies, iceray_kernel
+ * once, icesol_kernel once, icesol_spectrum_kernel once, one synchronisation.  n == 1 runs where
+ * airice_scalar_mode says: on the calling thread from the same source with no launch (the
+ * default), or through the same three kernels. */
+int airice_icesol_spectrum_host(const double *model3, const double *z0, const double *x1,
+                                const double *z1, size_t n, double a0, const double *freq_ghz,
+                                size_t n_freq, double *sol_out, size_t ld, uint8_t *status,
+                                double *att_out, size_t ld_f);
+
 /* --- in-ice interpolation tables ---------------------------------------------------------------
  * IceRayTracing::MakeTable (IceRayTracing.cc:2614-2724) and GetInterpolatedValue (.cc:2727-2905):
  * per antenna a grid of transmitter positions (xT, zT), 13 numbers per position, and the bilinear
@@ -756,7 +790,7 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
  * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
  * (airice_icetab_lookup_launch), "icepath_consts_kernel" and "icepath_kernel" (the two kernels of
- * airice_icepath_launch).
+ * airice_icepath_launch), "icesol_spectrum_kernel" (airice_icesol_spectrum_launch).
  * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -775,7 +809,7 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
  * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
  * (airice_icetab_lookup_launch), "icepath_consts_kernel", "icepath_kernel"
- * (airice_icepath_launch).
+ * (airice_icepath_launch), "icesol_spectrum_kernel" (airice_icesol_spectrum_launch).
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
