@@ -170,6 +170,33 @@ ICERAY_ITERS = 31              # false-position iterations of the direct search
 ICERAY_D, ICERAY_R, ICERAY_RA0, ICERAY_RA1 = 1, 2, 4, 8  # status: ray accepted
 ICERAY_NONFINITE = 128         # status: NaN or infinite input, no search
 ICERAY_DEFAULT_MODEL = (1.78, -0.43, 0.0132)  # A, B, C of n(z) = A + B exp(-C|z|)
+# airice_iceair_launch / _host (IceRayTracing::GetDirectRayPar_Air): the direct ray from the ice to
+# a receiver above the surface.
+ICEAIR_FIELDS = 10             # AIRICE_ICEAIR_FIELDS
+ICEAIR_RECEIVE_ANGLE = 0       # in air, deg; -1000 when |checkzero| > 0.5
+ICEAIR_LAUNCH_ANGLE = 1        # deg
+ICEAIR_TIME = 2                # s, as the reference forms it (air leg: horizontal distance / c)
+ICEAIR_LVALUE = 3
+ICEAIR_CHECKZERO = 4
+ICEAIR_STATUS = 5              # the status byte as a double
+ICEAIR_EVALS = 6               # residual evaluations
+ICEAIR_ITERS = 7               # false-position iterations
+ICEAIR_PHYSICAL_TIME = 8       # extension: ice time + h / (c cos(air angle))
+ICEAIR_PATH = 9                # extension: ice path + h / cos(air angle)
+ICEAIR_ACCEPTED = 1            # status: |checkzero| <= 0.5
+ICEAIR_NONFINITE = 128         # status: NaN or infinite input, no search
+# airice_icefirst_launch / _host (IceRayTracing::DirectRayTracer): the first-arriving ray of each
+# (emitter, antenna) pair.
+ICEFIRST_FIELDS = 8            # AIRICE_ICEFIRST_FIELDS
+ICEFIRST_LAUNCH_ANGLE = 0      # deg
+ICEFIRST_RECEIVE_ANGLE = 1     # deg
+ICEFIRST_PATH = 2              # m
+ICEFIRST_TIME_C = 3            # time * c, m
+ICEFIRST_TIME = 4              # s
+ICEFIRST_RAY_TYPE = 5          # 1 D, 3 Ra0, 4 Ra1 (the ICESOL_RAY_TYPE codes); 0 none
+ICEFIRST_X1 = 6                # sqrt(dx*dx + dy*dy)
+ICEFIRST_STATUS = 7            # the solver's status byte (ICERAY_* bits)
+PAIRS_ELEMENTWISE, PAIRS_CROSS = 0, 1  # AIRICE_PAIRS_*
 # airice_icesol_launch / _host (IceRayTracing::GetRayTracingSolutions, GetFocusingFactor): a column
 # base + k is slot k of the two rays a receiver sees, in order of arrival.
 ICESOL_FIELDS = 18             # AIRICE_ICESOL_FIELDS
@@ -210,6 +237,9 @@ EXPORTED_SYMBOLS = (
     "airice_rtf_eval_variant", "airice_air2ice_launch", "airice_air2ice_host",
     "airice_iceray_launch", "airice_iceray_host", "airice_icesol_launch", "airice_icesol_host",
     "airice_icesol_spectrum_launch", "airice_icesol_spectrum_host",
+    "airice_iceair_launch", "airice_iceair_host", "airice_icefirst_work_bytes",
+    "airice_icefirst_launch", "airice_icefirst_host", "airice_icefirst_select_launch",
+    "airice_icefirst_select_host",
     "airice_icetab_grid_init", "airice_icetab_grid", "airice_icetab_layout",
     "airice_icetab_pack_host", "airice_icetab_work_bytes", "airice_icetab_build_launch",
     "airice_icetab_build_host", "airice_icetab_lookup_launch", "airice_icetab_lookup_host",
@@ -301,6 +331,13 @@ def lib() -> ctypes.CDLL:
         "airice_icesol_host": ([P, P, P, P, S, D, D, I, P, S, P], I),
         "airice_icesol_spectrum_launch": ([P, P, P, P, S, P, S, S, D, P, S, P, S, P], I),
         "airice_icesol_spectrum_host": ([P, P, P, P, S, D, P, S, P, S, P, P, S], I),
+        "airice_iceair_launch": ([P, P, P, P, S, P, S, P, P], I),
+        "airice_iceair_host": ([P, P, P, P, S, P, S, P], I),
+        "airice_icefirst_work_bytes": ([S], S),
+        "airice_icefirst_launch": ([P, P, P, P, S, P, P, P, S, I, P, S, P, S, P, P], I),
+        "airice_icefirst_host": ([P, P, P, P, S, P, P, P, S, I, P, S, P], I),
+        "airice_icefirst_select_launch": ([P, S, P, S, P, S, P, P], I),
+        "airice_icefirst_select_host": ([P, S, P, S, P, S, P], I),
         "airice_icetab_grid_init": ([D, D, D, P], I),
         "airice_icetab_grid": ([D, D, D, D, ctypes.c_int32, ctypes.c_int32, D, P], I),
         "airice_icetab_layout": ([P, S, ctypes.POINTER(S)], I),

@@ -12,6 +12,8 @@
 
 #include "airice.h"
 #include "airice_host.h"
+#include "airice_iceair.hpp"
+#include "airice_icefirst.hpp"
 #include "airice_icepath.hpp"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
@@ -311,6 +313,25 @@ const char* icespec_bad_value(const double model[3], double a0) {
   return icesol_bad_value(model, a0, 1.0);
 }
 
+// The ice-to-air ray's host route: the lane function of iceair_kernel on the calling thread.
+void iceair_host_one(const double model[3], const double in[3], double* out10, uint8_t* status) {
+  const iceray::IceModel m = {model[0], model[1], model[2]};
+  const uint8_t st = iceair::solve_triple(m, in[0], in[1], in[2], iceray::ArrayOut{out10});
+  if (status != nullptr) *status = st;
+}
+
+// The first arrival's host route: the lane functions of icefirst_geom_kernel, iceray_kernel and
+// icefirst_select_kernel, one after the other, on the calling thread.
+void icefirst_host_one(const double model[3], const double in[6], double* out8, uint8_t* status) {
+  const iceray::IceModel m = {model[0], model[1], model[2]};
+  const double x1 = icefirst::horizontal_distance(in[0], in[1], in[3], in[4]);
+  double rays[iceray::kColumns];
+  iceray::solve_pair(m, in[2], x1, in[5], iceray::ArrayOut{rays});
+  const uint8_t st = icefirst::select_first([&](int c) { return rays[c]; }, x1,
+                                            [out8](int c, double v) { out8[c] = v; });
+  if (status != nullptr) *status = st;
+}
+
 }  // namespace airice
 
 using namespace airice;
@@ -321,6 +342,30 @@ const char* airice_last_error(void) { return g_err; }
 
 // One in-ice ray's path on the calling thread: the lane functions of icepath_consts_kernel and
 // icepath_kernel (airice_icepath.hpp compiled for the host).
+// The first-arrival choice over rows of the in-ice solver, on the calling thread: the lane
+// function of icefirst_select_kernel (airice_icefirst.hpp compiled for the host).
+int airice_icefirst_select_host(const double* rays, size_t ld_rays, const double* x1, size_t n,
+                                double* out, size_t ld, uint8_t* status) {
+  if (n == 0) return AIRICE_OK;
+  if (rays == nullptr || x1 == nullptr || out == nullptr) {
+    set_error("icefirst select: null argument (%s)",
+              rays == nullptr ? "rays" : x1 == nullptr ? "x1" : "out");
+    return AIRICE_EINVAL;
+  }
+  if (ld_rays < n || ld < n) {
+    set_error("icefirst select: %s (%zu) < n (%zu)", ld_rays < n ? "ld_rays" : "ld",
+              ld_rays < n ? ld_rays : ld, n);
+    return AIRICE_EINVAL;
+  }
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t st = icefirst::select_first(
+        [=](int c) { return rays[(size_t)c * ld_rays + i]; }, x1[i],
+        [=](int c, double v) { out[(size_t)c * ld + i] = v; });
+    if (status != nullptr) status[i] = st;
+  }
+  return AIRICE_OK;
+}
+
 int airice_icepath_one_host(const double* model3, int kind, double z0, double x1, double z1,
                             double L, double zmax, double* x, double* z, size_t cap,
                             int64_t* count) {

@@ -37,5 +37,12 @@ void icespec_host_one(const double model[3], const double in[3], double a0,
                       double* att0, double* att1);
 // The value checks the spectrum entries share: a0 and the model, as icesol_bad_value.
 const char* icespec_bad_value(const double model[3], double a0);
+// One (z0, x1, h) triple of the ice-to-air direct ray on the calling thread (airice_iceair.hpp
+// compiled for the host): out10 = the AIRICE_ICEAIR_FIELDS values, status nullable.
+void iceair_host_one(const double model[3], const double in[3], double* out10, uint8_t* status);
+// The first-arriving ray of one (emitter, antenna) pair on the calling thread
+// (airice_icefirst.hpp compiled for the host): in = xT, yT, zT, xR, yR, zR; out8 = the
+// AIRICE_ICEFIRST_FIELDS values, status nullable.
+void icefirst_host_one(const double model[3], const double in[6], double* out8, uint8_t* status);
 
 }  // namespace airice

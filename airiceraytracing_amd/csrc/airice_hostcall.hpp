@@ -123,9 +123,11 @@ struct Staged {
 // Uploads the k input columns cols[0 .. k-1] (n doubles each), runs launch(const Staged&) -- its
 // kernels go on the null stream -- and copies the outputs into the caller's columns of stride ld
 // (the padding [n, ld) of a column is left alone) and the status bytes into status (nullable).
+// lens (nullable): column j holds lens[j] <= n doubles, the rest of its n is left uninitialised.
 template <class Launch>
-int staged_call(const double* const* cols, size_t k, size_t n, size_t scratch_doubles, int fields,
-                double* out, size_t ld, uint8_t* status, Launch launch) {
+int staged_call(const double* const* cols, const size_t* lens, size_t k, size_t n,
+                size_t scratch_doubles, int fields, double* out, size_t ld, uint8_t* status,
+                Launch launch) {
   DevBuffer buf;
   HIP_TRY(buf.alloc(sizeof(double) * ((k + (size_t)fields) * n + scratch_doubles) + n));
   Staged s;
@@ -135,13 +137,19 @@ int staged_call(const double* const* cols, size_t k, size_t n, size_t scratch_do
   s.out = s.scratch + scratch_doubles;
   s.status = reinterpret_cast<uint8_t*>(s.out + (size_t)fields * n);
   for (size_t j = 0; j < k; ++j)
-    HIP_TRY(hipMemcpy(s.col(j), cols[j], sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(s.col(j), cols[j], sizeof(double) * (lens != nullptr ? lens[j] : n),
+                      hipMemcpyHostToDevice));
   if (int rc = launch(s)) return rc;
   // the copy-back is on the null stream, like the launches: it waits for the kernels
   HIP_TRY(hipMemcpy2D(out, sizeof(double) * ld, s.out, sizeof(double) * n, sizeof(double) * n,
                       (size_t)fields, hipMemcpyDeviceToHost));
   if (status != nullptr) HIP_TRY(hipMemcpy(status, s.status, n, hipMemcpyDeviceToHost));
   return AIRICE_OK;
+}
+template <class Launch>
+int staged_call(const double* const* cols, size_t k, size_t n, size_t scratch_doubles, int fields,
+                double* out, size_t ld, uint8_t* status, Launch launch) {
+  return staged_call(cols, nullptr, k, n, scratch_doubles, fields, out, ld, status, launch);
 }
 
 // The n == 1 form of the same hand-over: one value per column, and the status byte.

@@ -3,7 +3,7 @@
 // The kernels live in airice_table.hip (forward ray: table, rays), airice_solve.hip (minimizer),
 // airice_lookup.hip (the lookup's pack kernels), airice_path.hip, airice_rtf.hip and the in-ice
 // units (airice_iceray.hip, airice_icesol.hip, airice_icespec.hip, airice_icetab.hip,
-// airice_icepath.hip); each opens with its own inventory.
+// airice_icepath.hip, airice_iceair.hip, airice_icefirst.hip); each opens with its own inventory.
 // Data layout in HBM: structure-of-arrays, column c of item i at out[c*ld + i], so each
 // wave's store of one column is one contiguous 256 B (f32) / 512 B (f64) segment.
 #pragma once
@@ -148,6 +148,26 @@ AIRICE_LOCAL int launch_icespec(const double model[3], double a0, const double* 
                                 const double* z1, const double* rays, size_t ld_rays,
                                 const double* sol, size_t ld_sol, size_t n, const double* freq,
                                 size_t n_freq, double* att, size_t ld_f, hipStream_t st);
+// The ice-to-air direct ray, batched (airice_iceair.hip): iceair_kernel, one (z0, x1, h) triple per
+// lane, AIRICE_ICEAIR_FIELDS columns of stride ld and a status byte (nullable).  The lane's
+// function on the calling thread is iceair_host_one (airice_host.h).
+AIRICE_LOCAL int launch_iceair(const double model[3], const double* z0, const double* x1,
+                               const double* h, size_t n, double* out, size_t ld, uint8_t* status,
+                               hipStream_t st);
+// The first-arriving ray of n (emitter, antenna) pairs (airice_icefirst.hip): icefirst_geom_kernel,
+// iceray_kernel and icefirst_select_kernel over work (icefirst::kWorkDoubles doubles per pair);
+// cross: pair t*n_rx + r, else pair i = (tx i, rx i).  AIRICE_ICEFIRST_FIELDS columns of stride ld
+// and a status byte (nullable).  One pair on the calling thread is icefirst_host_one.
+AIRICE_LOCAL int launch_icefirst(const double model[3], const double* tx_x, const double* tx_y,
+                                 const double* tx_z, const double* rx_x, const double* rx_y,
+                                 const double* rx_z, size_t n_rx, bool cross, size_t n,
+                                 double* work, double* out, size_t ld, uint8_t* status,
+                                 hipStream_t st);
+
+// The last of those launches on its own: the choice over rows launch_iceray wrote (stride ld_rays).
+AIRICE_LOCAL int launch_icefirst_select(const double* rays, size_t ld_rays, const double* x1,
+                                        size_t n, double* out, size_t ld, uint8_t* status,
+                                        hipStream_t st);
 
 static_assert(kMaxParsedLayers == kMaxLayers, "parse and kernels agree on the layer count");
 
@@ -224,6 +244,9 @@ enum KTimerId {
   KT_ICEPATH_CONSTS,
   KT_ICEPATH,
   KT_ICESPEC,
+  KT_ICEAIR,
+  KT_ICEFIRST_GEOM,
+  KT_ICEFIRST_SELECT,
   KT_COUNT
 };
 extern std::atomic<bool> g_ktimer_on;
@@ -261,6 +284,9 @@ enum LaunchId {
   LC_ICEPATH_CONSTS, // icepath_consts_kernel (an in-ice path batch's per-ray records)
   LC_ICEPATH,       // icepath_kernel (the in-ice ray-path samples)
   LC_ICESPEC,       // icesol_spectrum_kernel (the two rays' attenuation over a frequency grid)
+  LC_ICEAIR,        // iceair_kernel (batched ice-to-air direct ray)
+  LC_ICEFIRST_GEOM, // icefirst_geom_kernel (a first-arrival batch's (z0, x1, z1) triples)
+  LC_ICEFIRST_SELECT, // icefirst_select_kernel (the first-arriving ray of each pair)
   LC_COUNT
 };
 extern std::atomic<long long> g_launches[LC_COUNT];

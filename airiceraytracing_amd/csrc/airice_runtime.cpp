@@ -18,6 +18,7 @@
 
 #include "airice.h"
 #include "airice_hostcall.hpp"
+#include "airice_icefirst.hpp"
 #include "airice_internal.h"
 
 namespace airice {
@@ -211,7 +212,9 @@ static const char* const kKtNames[KT_COUNT] = {"table_kernel",      "roots_kerne
                                                "icesol_kernel",     "icetab_points_kernel",
                                                "icetab_pack_kernel", "icetab_lookup_kernel",
                                                "icepath_consts_kernel", "icepath_kernel",
-                                               "icesol_spectrum_kernel"};
+                                               "icesol_spectrum_kernel", "iceair_kernel",
+                                               "icefirst_geom_kernel",
+                                               "icefirst_select_kernel"};
 static_assert(sizeof(kKtNames) / sizeof(kKtNames[0]) == KT_COUNT, "one name per timer");
 
 std::atomic<long long> g_launches[LC_COUNT];
@@ -221,7 +224,8 @@ static const char* const kLcNames[LC_COUNT] = {
     "single_ray_kernel",   "path_kernel",  "ray_consts_kernel", "ray_paths_kernel",
     "lookup_multi_kernel", "air2ice_kernel", "air_part_kernel", "iceray_kernel",
     "icesol_kernel", "icetab_points_kernel", "icetab_pack_kernel", "icetab_lookup_kernel",
-    "icepath_consts_kernel", "icepath_kernel", "icesol_spectrum_kernel"};
+    "icepath_consts_kernel", "icepath_kernel", "icesol_spectrum_kernel", "iceair_kernel",
+    "icefirst_geom_kernel", "icefirst_select_kernel"};
 static_assert(sizeof(kLcNames) / sizeof(kLcNames[0]) == LC_COUNT, "one name per counter");
 
 // AIRICE_LAUNCH_REPORT=1: the counts go to stderr when the library unloads (the CLI tests read
@@ -968,6 +972,150 @@ int airice_iceray_host(const double* model3, const double* z0, const double* x1,
   return staged_call(cols, 3, n, 0, kF, out, ld, status, [&](const Staged& s) {
     return airice_iceray_launch(model3, s.col(0), s.col(1), s.col(2), n, s.out, n, s.status,
                                 nullptr);
+  });
+}
+
+// ---- the ice-to-air direct ray (IceRayTracing::GetDirectRayPar_Air), batched --------------------
+int airice_iceair_launch(const double* model3, const double* d_z0, const double* d_x1,
+                         const double* d_h, size_t n, double* d_out, size_t ld, uint8_t* d_status,
+                         void* stream) {
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("iceair", {{"z0", d_z0}, {"x1", d_x1}, {"h", d_h}, {"out", d_out}}))
+    return rc;
+  if (int rc = short_stride("iceair", "ld", ld, n)) return rc;
+  if (int rc = exceeds_one_launch("iceair", n)) return rc;
+  return airice::launch_iceair(ice_model_or_default(model3), d_z0, d_x1, d_h, n, d_out, ld,
+                               d_status, (hipStream_t)stream);
+}
+
+int airice_iceair_host(const double* model3, const double* z0, const double* x1, const double* h,
+                       size_t n, double* out, size_t ld, uint8_t* status) {
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("iceair", {{"z0", z0}, {"x1", x1}, {"h", h}, {"out", out}}))
+    return rc;
+  if (int rc = short_stride("iceair", "ld", ld, n)) return rc;
+  constexpr int kF = AIRICE_ICEAIR_FIELDS;
+  if (n == 1) {  // one triple: where airice_scalar_mode says
+    const double in[3] = {z0[0], x1[0], h[0]};
+    double o[kF];
+    uint8_t st = 0;
+    if (airice::scalar_on_host()) {
+      airice::iceair_host_one(ice_model_or_default(model3), in, o, &st);
+    } else if (int rc = slot_call(in, 3, 0, o, kF, &st, 1, kNoSignal, [&](const SlotArgs& s) {
+                 return airice_iceair_launch(model3, s.in, s.in + 1, s.in + 2, 1, s.out, 1, s.flag,
+                                             s.st);
+               })) {
+      return rc;
+    }
+    scatter_one(o, kF, st, out, ld, status);
+    return AIRICE_OK;
+  }
+  const double* cols[3] = {z0, x1, h};
+  return staged_call(cols, 3, n, 0, kF, out, ld, status, [&](const Staged& s) {
+    return airice_iceair_launch(model3, s.col(0), s.col(1), s.col(2), n, s.out, n, s.status,
+                                nullptr);
+  });
+}
+
+// ---- the first-arriving ray between 3-D points (IceRayTracing::DirectRayTracer), batched --------
+size_t airice_icefirst_work_bytes(size_t n_pairs) {
+  return sizeof(double) * (size_t)airice::icefirst::kWorkDoubles * n_pairs;
+}
+
+// The pairs of a first-arrival call, or what is wrong with its pairing and counts.
+static int icefirst_pairs(size_t n_tx, size_t n_rx, int pairing, size_t* n_pairs) {
+  if (pairing != AIRICE_PAIRS_ELEMENTWISE && pairing != AIRICE_PAIRS_CROSS) {
+    set_error("icefirst: unknown pairing %d", pairing);
+    return AIRICE_EINVAL;
+  }
+  if (pairing == AIRICE_PAIRS_ELEMENTWISE && n_tx != n_rx) {
+    set_error("icefirst: n_tx (%zu) != n_rx (%zu) with AIRICE_PAIRS_ELEMENTWISE", n_tx, n_rx);
+    return AIRICE_EINVAL;
+  }
+  if (pairing == AIRICE_PAIRS_CROSS && n_rx != 0 && n_tx > ((size_t)1 << 46) / n_rx) {
+    set_error("icefirst: n_tx (%zu) x n_rx (%zu) exceeds one launch", n_tx, n_rx);
+    return AIRICE_EINVAL;
+  }
+  *n_pairs = pairing == AIRICE_PAIRS_CROSS ? n_tx * n_rx : n_tx;
+  return AIRICE_OK;
+}
+
+int airice_icefirst_launch(const double* model3, const double* d_tx_x, const double* d_tx_y,
+                           const double* d_tx_z, size_t n_tx, const double* d_rx_x,
+                           const double* d_rx_y, const double* d_rx_z, size_t n_rx, int pairing,
+                           void* d_work, size_t work_bytes, double* d_out, size_t ld,
+                           uint8_t* d_status, void* stream) {
+  size_t n = 0;
+  if (int rc = icefirst_pairs(n_tx, n_rx, pairing, &n)) return rc;
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("icefirst", {{"tx_x", d_tx_x}, {"tx_y", d_tx_y}, {"tx_z", d_tx_z},
+                                          {"rx_x", d_rx_x}, {"rx_y", d_rx_y}, {"rx_z", d_rx_z},
+                                          {"work", d_work}, {"out", d_out}}))
+    return rc;
+  if (int rc = short_stride("icefirst", "ld", ld, n)) return rc;
+  if (int rc = exceeds_one_launch("icefirst", n)) return rc;
+  if (work_bytes < airice_icefirst_work_bytes(n)) {
+    set_error("icefirst: work_bytes (%zu) < airice_icefirst_work_bytes(%zu) = %zu", work_bytes, n,
+              airice_icefirst_work_bytes(n));
+    return AIRICE_EINVAL;
+  }
+  return airice::launch_icefirst(ice_model_or_default(model3), d_tx_x, d_tx_y, d_tx_z, d_rx_x,
+                                 d_rx_y, d_rx_z, n_rx, pairing == AIRICE_PAIRS_CROSS, n,
+                                 static_cast<double*>(d_work), d_out, ld, d_status,
+                                 (hipStream_t)stream);
+}
+
+int airice_icefirst_select_launch(const double* d_rays, size_t ld_rays, const double* d_x1,
+                                  size_t n, double* d_out, size_t ld, uint8_t* d_status,
+                                  void* stream) {
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("icefirst select", {{"rays", d_rays}, {"x1", d_x1}, {"out", d_out}}))
+    return rc;
+  if (int rc = short_stride("icefirst select", "ld_rays", ld_rays, n)) return rc;
+  if (int rc = short_stride("icefirst select", "ld", ld, n)) return rc;
+  if (int rc = exceeds_one_launch("icefirst select", n)) return rc;
+  return airice::launch_icefirst_select(d_rays, ld_rays, d_x1, n, d_out, ld, d_status,
+                                        (hipStream_t)stream);
+}
+
+int airice_icefirst_host(const double* model3, const double* tx_x, const double* tx_y,
+                         const double* tx_z, size_t n_tx, const double* rx_x, const double* rx_y,
+                         const double* rx_z, size_t n_rx, int pairing, double* out, size_t ld,
+                         uint8_t* status) {
+  size_t n = 0;
+  if (int rc = icefirst_pairs(n_tx, n_rx, pairing, &n)) return rc;
+  if (n == 0) return AIRICE_OK;
+  if (int rc = null_argument("icefirst", {{"tx_x", tx_x}, {"tx_y", tx_y}, {"tx_z", tx_z},
+                                          {"rx_x", rx_x}, {"rx_y", rx_y}, {"rx_z", rx_z},
+                                          {"out", out}}))
+    return rc;
+  if (int rc = short_stride("icefirst", "ld", ld, n)) return rc;
+  constexpr int kF = AIRICE_ICEFIRST_FIELDS, kW = airice::icefirst::kWorkDoubles;
+  if (n == 1) {  // one pair: where airice_scalar_mode says
+    const double in[6] = {tx_x[0], tx_y[0], tx_z[0], rx_x[0], rx_y[0], rx_z[0]};
+    double o[kF];
+    uint8_t st = 0;
+    if (airice::scalar_on_host()) {
+      airice::icefirst_host_one(ice_model_or_default(model3), in, o, &st);
+    } else if (int rc = slot_call(in, 6, kW, o, kF, &st, 1, kNoSignal,  // three launches
+                                  [&](const SlotArgs& s) {
+                                    return airice_icefirst_launch(
+                                        model3, s.in, s.in + 1, s.in + 2, 1, s.in + 3, s.in + 4,
+                                        s.in + 5, 1, AIRICE_PAIRS_ELEMENTWISE, s.scratch,
+                                        sizeof(double) * kW, s.out, 1, s.flag, s.st);
+                                  })) {
+      return rc;
+    }
+    scatter_one(o, kF, st, out, ld, status);
+    return AIRICE_OK;
+  }
+  // six input columns of stride n: an emitter column holds n_tx values, an antenna column n_rx
+  const double* cols[6] = {tx_x, tx_y, tx_z, rx_x, rx_y, rx_z};
+  const size_t lens[6] = {n_tx, n_tx, n_tx, n_rx, n_rx, n_rx};
+  return staged_call(cols, lens, 6, n, (size_t)kW * n, kF, out, ld, status, [&](const Staged& s) {
+    return airice_icefirst_launch(model3, s.col(0), s.col(1), s.col(2), n_tx, s.col(3), s.col(4),
+                                  s.col(5), n_rx, pairing, s.scratch, sizeof(double) * kW * n,
+                                  s.out, n, s.status, nullptr);
   });
 }
 

@@ -6,7 +6,8 @@
 // function airice_icesol_host runs for n = 1), the attenuation functions airice_icesol.hpp's,
 // GetAttenuationSpectrum icespec_host_one (airice_icespec.hpp); the
 // GetFull*RayPath samplers and PlotAndStoreRays are airice_icepath.hpp (bit for bit
-// airice_icepath_one_host).  No HIP here, so this file also builds into the sanitizer driver
+// airice_icepath_one_host); fDa_Air and GetDirectRayPar_Air are airice_iceair.hpp (iceair_host_one,
+// the function airice_iceair_host runs for n = 1), DirectRayTracer icefirst_host_one.  No HIP here, so this file also builds into the sanitizer driver
 // (tests/cpp/iceray_driver.cpp, `make iceray_asan`).
 // The interpolation tables (SetNumberOfAntennas, MakeTable, GetInterpolatedValue and their
 // extensions, at the end) keep one image per antenna in host memory and read it on the calling
@@ -23,6 +24,7 @@
 
 #include "IceRayTracing.hh"
 #include "airice_host.h"
+#include "airice_iceair.hpp"
 #include "airice_icepath.hpp"
 #include "airice_iceray.hpp"
 #include "airice_icesol.hpp"
@@ -42,6 +44,7 @@ int airice_memcpy_d2h(void *, const void *, size_t) __attribute__((weak));
 }
 
 namespace ir = airice::iceray;
+namespace ia = airice::iceair;
 namespace is = airice::icesol;
 namespace it = airice::icetab;
 namespace ip = airice::icepath;
@@ -197,6 +200,36 @@ double *IceRayTracing(double /*x0*/, double z0, double x1, double z1) {
   airice::iceray_host_one(m, in, all, nullptr);
   double *output = new double[AIRICE_ICERAY_REFERENCE_FIELDS];
   for (int c = 0; c < AIRICE_ICERAY_REFERENCE_FIELDS; c++) output[c] = all[c];
+  return output;
+}
+
+// fDa_Air (.cc:2358-2408): z1 is the receiver's height above the surface
+double fDa_Air(double x, void *params) {
+  const fDanfRa_params *p = static_cast<const fDanfRa_params *>(params);
+  ia::Triple t = ia::make_triple(ir::IceModel{p->a, B_ice, C_ice}, p->z0, p->x1, p->z1);
+  return ia::residual(t, x);
+}
+
+// GetDirectRayPar_Air (.cc:2411-2500): columns 0-4 of the ice-to-air solve's host route
+double *GetDirectRayPar_Air(double z0, double x1, double z1) {
+  const double m[3] = {A_ice, B_ice, C_ice};
+  const double in[3] = {z0, x1, z1};
+  double all[AIRICE_ICEAIR_FIELDS];
+  airice::iceair_host_one(m, in, all, nullptr);
+  double *output = new double[5];
+  std::copy(all, all + 5, output);
+  return output;
+}
+
+// DirectRayTracer (.cc:2502-2612): columns 0-4 of the first arrival's host route.  Five values:
+// the reference allocates four and writes five.
+double *DirectRayTracer(double xT, double yT, double zT, double xR, double yR, double zR) {
+  const double m[3] = {A_ice, B_ice, C_ice};
+  const double in[6] = {xT, yT, zT, xR, yR, zR};
+  double all[AIRICE_ICEFIRST_FIELDS];
+  airice::icefirst_host_one(m, in, all, nullptr);
+  double *output = new double[5];
+  std::copy(all, all + 5, output);
   return output;
 }
 

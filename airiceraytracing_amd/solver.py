@@ -649,6 +649,125 @@ class AirIceSolver:
                                        ptr(st)), "airice_iceray_host")
         return out, st
 
+    # ------------------------------------------------------------------ ice-to-air rays, batched
+    def ice_to_air_device(self, z0, x1, h, out, status=None, ld: int | None = None, stream=None,
+                          model=None) -> None:
+        """airice_iceair_launch: IceRayTracing::GetDirectRayPar_Air -- the direct ray from a
+        transmitter at depth ``z0`` (<= 0, in the ice) to a receiver ``x1`` metres away and ``h``
+        metres above the surface -- for n triples in one launch.  ``z0``, ``x1``, ``h`` (n float64
+        each), ``out`` (10 x ld float64: the _lib.ICEAIR_* columns) and ``status`` (n uint8,
+        optional: _lib.ICEAIR_ACCEPTED / _NONFINITE) are device tensors; ``model`` as
+        ``ice_rays_device``.  Stream-ordered."""
+        n = int(z0.numel())
+        m = self._ice_model(model)
+        check(lib().airice_iceair_launch(ptr(m), ptr(z0), ptr(x1), ptr(h), n, ptr(out),
+                                         n if ld is None else ld, ptr(status),
+                                         _stream_handle(stream)), "airice_iceair_launch")
+
+    def ice_to_air_host(self, z0, x1, h, model=None):
+        """airice_iceair_host: numpy in, numpy out; the three inputs broadcast against each other.
+        Returns (out (10, n), status (n) uint8).  One triple runs where scalar_mode() says (the
+        calling thread by default); more are copied to the GPU, solved in one launch and copied
+        back."""
+        arrs = np.broadcast_arrays(*[np.asarray(a, dtype=np.float64) for a in (z0, x1, h)])
+        a, b, c = [np.ascontiguousarray(v).ravel() for v in arrs]
+        n = a.size
+        out = np.empty((_lib.ICEAIR_FIELDS, n), dtype=np.float64)
+        st = np.empty(n, dtype=np.uint8)
+        m = self._ice_model(model)
+        check(lib().airice_iceair_host(ptr(m), ptr(a), ptr(b), ptr(c), n, ptr(out), max(n, 1),
+                                       ptr(st)), "airice_iceair_host")
+        return out, st
+
+    # ------------------------------------------------------------------ first arrivals, batched
+    _PAIRINGS = {"elementwise": _lib.PAIRS_ELEMENTWISE, "cross": _lib.PAIRS_CROSS}
+
+    @classmethod
+    def _pairing(cls, pairing, n_tx: int, n_rx: int) -> tuple[int, int]:
+        """(the AIRICE_PAIRS_* code, the number of pairs) of a first-arrival call."""
+        if pairing not in cls._PAIRINGS:
+            raise ValueError(f"pairing: 'elementwise' or 'cross', got {pairing!r}")
+        if pairing == "elementwise" and n_tx != n_rx:
+            raise ValueError(f"elementwise pairing: {n_tx} emitters, {n_rx} antennas")
+        return cls._PAIRINGS[pairing], n_tx * n_rx if pairing == "cross" else n_tx
+
+    @staticmethod
+    def ice_first_arrivals_work_bytes(n_pairs: int) -> int:
+        """airice_icefirst_work_bytes: the device work buffer of ``n_pairs`` pairs."""
+        return int(lib().airice_icefirst_work_bytes(n_pairs))
+
+    def ice_first_arrivals_device(self, tx, rx, out, work=None, pairing: str = "elementwise",
+                                  status=None, ld: int | None = None, stream=None, model=None):
+        """airice_icefirst_launch: IceRayTracing::DirectRayTracer -- the first-arriving ray from
+        each emitter to each antenna -- in three launches (geometry, the in-ice solve, the choice).
+        ``tx`` (3 x n_tx) and ``rx`` (3 x n_rx) are float64 device tensors of x, y, z rows (z
+        negative, in the ice); ``pairing`` is "elementwise" (n_tx == n_rx, pair i) or "cross" (pair
+        t * n_rx + r); ``out`` (8 x ld float64: the _lib.ICEFIRST_* columns) and ``status`` (one
+        uint8 per pair, optional: the solver's _lib.ICERAY_* bits) are device tensors.  ``work`` is
+        a device buffer of ``ice_first_arrivals_work_bytes(pairs)`` bytes; None allocates one with
+        torch on ``tx``'s device.  Returns the work buffer, which must stay alive until the
+        launches have run.  Stream-ordered."""
+        for name, a in (("tx", tx), ("rx", rx)):
+            if a.dim() != 2 or a.shape[0] != 3 or (a.shape[1] > 1 and a.stride(1) != 1):
+                raise ValueError(f"{name}: a (3, n) tensor with contiguous rows")
+        n_tx, n_rx = int(tx.shape[1]), int(rx.shape[1])
+        code, pairs = self._pairing(pairing, n_tx, n_rx)
+        need = self.ice_first_arrivals_work_bytes(pairs)
+        if work is None:
+            import torch
+            work = torch.empty(max(need, 1), dtype=torch.uint8, device=tx.device)
+        m = self._ice_model(model)
+        check(lib().airice_icefirst_launch(
+            ptr(m), ptr(tx[0]), ptr(tx[1]), ptr(tx[2]), n_tx, ptr(rx[0]), ptr(rx[1]), ptr(rx[2]),
+            n_rx, code, ptr(work), int(work.numel() * work.element_size()), ptr(out),
+            pairs if ld is None else ld, ptr(status), _stream_handle(stream)),
+            "airice_icefirst_launch")
+        return work
+
+    def ice_first_arrivals_host(self, tx, rx, pairing: str = "elementwise", model=None):
+        """airice_icefirst_host: ``tx`` (3, n_tx) and ``rx`` (3, n_rx) numpy arrays in,
+        (out (8, pairs), status (pairs) uint8) out.  One pair runs where scalar_mode() says (the
+        calling thread by default); more are copied to the GPU, traced in three launches and
+        copied back."""
+        t = np.ascontiguousarray(np.asarray(tx, dtype=np.float64).reshape(3, -1))
+        r = np.ascontiguousarray(np.asarray(rx, dtype=np.float64).reshape(3, -1))
+        code, pairs = self._pairing(pairing, t.shape[1], r.shape[1])
+        out = np.empty((_lib.ICEFIRST_FIELDS, pairs), dtype=np.float64)
+        st = np.empty(pairs, dtype=np.uint8)
+        m = self._ice_model(model)
+        check(lib().airice_icefirst_host(ptr(m), ptr(t[0]), ptr(t[1]), ptr(t[2]), t.shape[1],
+                                         ptr(r[0]), ptr(r[1]), ptr(r[2]), r.shape[1], code,
+                                         ptr(out), max(pairs, 1), ptr(st)),
+              "airice_icefirst_host")
+        return out, st
+
+    def ice_first_select_device(self, rays, x1, out, status=None, ld: int | None = None,
+                                ld_rays: int | None = None, stream=None) -> None:
+        """airice_icefirst_select_launch: the first-arrival choice alone, over ``rays`` (32 x
+        ld_rays float64, what ``ice_rays_device`` wrote) with ``x1`` (n float64) passed through to
+        column 6, in one launch.  ``out`` (8 x ld float64) and ``status`` (n uint8, optional) as
+        ``ice_first_arrivals_device``; device tensors.  Stream-ordered."""
+        n = int(x1.numel())
+        check(lib().airice_icefirst_select_launch(ptr(rays), n if ld_rays is None else ld_rays,
+                                                  ptr(x1), n, ptr(out), n if ld is None else ld,
+                                                  ptr(status), _stream_handle(stream)),
+              "airice_icefirst_select_launch")
+
+    @staticmethod
+    def ice_first_select_host(rays, x1):
+        """airice_icefirst_select_host: the same choice over host rows ``rays`` (32, n) on the
+        calling thread, no GPU.  Returns (out (8, n), status (n) uint8)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64)
+        x = np.ascontiguousarray(x1, dtype=np.float64).ravel()
+        n = x.size
+        if r.shape != (_lib.ICERAY_FIELDS, n):
+            raise ValueError(f"rays: ({_lib.ICERAY_FIELDS}, {n}), got {r.shape}")
+        out = np.empty((_lib.ICEFIRST_FIELDS, n), dtype=np.float64)
+        st = np.empty(n, dtype=np.uint8)
+        check(lib().airice_icefirst_select_host(ptr(r), max(n, 1), ptr(x), n, ptr(out), max(n, 1),
+                                                ptr(st)), "airice_icefirst_select_host")
+        return out, st
+
     # ------------------------------------------------------------------ in-ice ray paths, batched
     @staticmethod
     def _ice_ray_paths_plan(z0, z1, status, rays: int):

@@ -49,8 +49,19 @@
  *     formed about the turning depth of L without cancellation; nothing is appended for a
  *     non-finite argument or a depth above 0 or below -50,000 m.  PlotAndStoreRays calls the three
  *     under the reference's conditions and, like it, discards the vectors.
- * Not provided: the _Cnz and _Air variants, DirectRayTracer, and FindFunctionRoot* with GSL-typed
- * arguments.
+ *   - fDa_Air and GetDirectRayPar_Air are the ice-to-air direct ray: z1 is the receiver's height
+ *     ABOVE the surface.  GetDirectRayPar_Air returns new double[5], on the calling thread (bit
+ *     for bit airice_iceair_host with n = 1; batches: GetDirectRayPar_AirBatch).  Differences
+ *     (DESIGN.md §13): the receive angle in ice is asin(L/n(1e-7)), not atan of a
+ *     gsl_deriv_central slope; the air leg's tangent is L / sqrt((1-L)(1+L)), not the tangent of
+ *     the rounded air angle, which loses 1/(1-L^2) ulps at a grazing exit; the reference's
+ *     quirks are kept -- its time adds the air leg's
+ *     HORIZONTAL distance over c (airice_iceair_host's column 8 has the physical time), and its
+ *     NaN fallbacks put degrees where radians are read.
+ *   - DirectRayTracer is the first-arriving ray between two 3-D points in the ice (bit for bit
+ *     airice_icefirst_host with one pair; batches: DirectRayTracerBatch).  Difference: it
+ *     returns new double[5] -- the reference allocates four doubles and writes five.
+ * Not provided: the _Cnz variants and FindFunctionRoot* with GSL-typed arguments.
  * Link: -L<repo>/airiceraytracing_amd -lairice. */
 #ifndef AIRICE_ICERAYTRACING_HH_
 #define AIRICE_ICERAYTRACING_HH_
@@ -107,6 +118,15 @@ double *GetReflectedRayPar(double z0, double x1, double z1);
 double *GetRefractedRayPar(double z0, double x1, double z1, double LangR, double RangR,
                            double checkzeroD, double checkzeroR);
 double *IceRayTracing(double x0, double z0, double x1, double z1);
+
+/* The direct ray to a receiver z1 metres above the surface (.cc:2358-2500); params: fDanfRa_params.
+ * output[0..4]: receive angle in air (deg; -1000: rejected), launch angle (deg), time (s), L,
+ * checkzero. */
+double fDa_Air(double x, void *params);
+double *GetDirectRayPar_Air(double z0, double x1, double z1);
+/* The first-arriving ray between two points in the ice (.cc:2502-2612): launch angle, receive
+ * angle, geometric path, time*c, time; -1000 in all five when no ray arrives. */
+double *DirectRayTracer(double xT, double yT, double zT, double xR, double yR, double zR);
 
 /* The sampled ray paths (.cc:1257-1743): x and z are appended to */
 void GetFullDirectRayPath(double z0, double x1, double z1, double lvalueD, std::vector<double> &x,
@@ -169,6 +189,25 @@ inline int IceRayTracingBatch(const double *z0, const double *x1, const double *
                               double *out, size_t ld, uint8_t *status) {
   const double model[3] = {A_ice, B_ice, C_ice};
   return airice_iceray_host(model, z0, x1, z1, n, out, ld, status);
+}
+
+/* GetDirectRayPar_Air of n (Tx depth, distance, Rx height) triples in one launch of iceair_kernel:
+ * value c of triple i at out[c*ld + i] (AIRICE_ICEAIR_FIELDS columns), status (nullable) the
+ * AIRICE_ICEAIR_* bits (airice_iceair_host, include/airice.h). */
+inline int GetDirectRayPar_AirBatch(const double *z0, const double *x1, const double *z1, size_t n,
+                                    double *out, size_t ld, uint8_t *status) {
+  const double model[3] = {A_ice, B_ice, C_ice};
+  return airice_iceair_host(model, z0, x1, z1, n, out, ld, status);
+}
+
+/* DirectRayTracer of emitters x antennas (pairing: AIRICE_PAIRS_ELEMENTWISE or AIRICE_PAIRS_CROSS):
+ * value c of pair i at out[c*ld + i] (AIRICE_ICEFIRST_FIELDS columns), status (nullable) the
+ * solver's AIRICE_ICERAY_* bits (airice_icefirst_host, include/airice.h). */
+inline int DirectRayTracerBatch(const double *xT, const double *yT, const double *zT, size_t n_tx,
+                                const double *xR, const double *yR, const double *zR, size_t n_rx,
+                                int pairing, double *out, size_t ld, uint8_t *status) {
+  const double model[3] = {A_ice, B_ice, C_ice};
+  return airice_icefirst_host(model, xT, yT, zT, n_tx, xR, yR, zR, n_rx, pairing, out, ld, status);
 }
 
 /* GetRayTracingSolutions -- and, with focusing != 0, GetFocusingFactor -- of n (Tx depth,

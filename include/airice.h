@@ -508,6 +508,104 @@ int airice_iceray_launch(const double *model3, const double *d_z0, const double 
 int airice_iceray_host(const double *model3, const double *z0, const double *x1, const double *z1,
                        size_t n, double *out, size_t ld, uint8_t *status);
 
+/* --- ice-to-air direct ray (IceRayTracing::GetDirectRayPar_Air, IceRayTracing.cc:2358-2500) ------
+ * The direct ray from a transmitter at depth d_z0 (<= 0) in the ice to a receiver d_x1 metres away
+ * and d_h (> 0) metres ABOVE the surface -- refracting in the ice, straight in the air at n = 1 --
+ * for n triples in ONE launch of iceair_kernel, one triple per lane: the reference's false
+ * position of fDa_Air on [1e-7, min(n(1e-7), n(z0))] (GSL semantics restated, at most 100
+ * iterations) and its closing arithmetic as written, with the receive angle in ice taken as
+ * asin(L/n(1e-7)) and the air angle's tangent and cosine taken from its sine, L (DESIGN.md §8,
+ * §13).  model3 as airice_iceray_launch.
+ * Value c of triple i lands at d_out[c*ld + i]:
+ *   0 receive angle in air, deg (-1000 when |checkzero| > 0.5); 1 launch angle, deg; 2 time, s, as
+ *   the reference forms it -- its air leg is the HORIZONTAL distance over c; 3 L; 4 checkzero;
+ *   5 status byte as a double; 6 residual evaluations; 7 false-position iterations;
+ *   8 (extension) the physical time, ice time + h / (c cos(air angle)); 9 (extension) the
+ *   geometric path, ice path + h / cos(air angle).
+ * Status (also d_status, nullable): AIRICE_ICEAIR_ACCEPTED when |checkzero| <= 0.5;
+ * AIRICE_ICEAIR_NONFINITE alone for a NaN or infinite input, whose columns 0-4 and 8-9 are NaN and
+ * for which no search runs.  No other input is special: h <= 0 or z0 > 0 run the arithmetic as
+ * written.  Triples are independent: results do not depend on the batch or its order.
+ * Stream-ordered, no device allocation, exactly one kernel launch; n == 0 is AIRICE_OK and nothing
+ * is launched; a null required pointer or ld < n is AIRICE_EINVAL before any device call, and
+ * airice_last_error() names the argument. */
+#define AIRICE_ICEAIR_FIELDS 10
+#define AIRICE_ICEAIR_RECEIVE_ANGLE 0
+#define AIRICE_ICEAIR_LAUNCH_ANGLE 1
+#define AIRICE_ICEAIR_TIME 2
+#define AIRICE_ICEAIR_LVALUE 3
+#define AIRICE_ICEAIR_CHECKZERO 4
+#define AIRICE_ICEAIR_STATUS 5
+#define AIRICE_ICEAIR_EVALS 6
+#define AIRICE_ICEAIR_ITERS 7
+#define AIRICE_ICEAIR_PHYSICAL_TIME 8
+#define AIRICE_ICEAIR_PATH 9
+#define AIRICE_ICEAIR_ACCEPTED 1
+#define AIRICE_ICEAIR_NONFINITE 128
+int airice_iceair_launch(const double *model3, const double *d_z0, const double *d_x1,
+                         const double *d_h, size_t n, double *d_out, size_t ld,
+                         uint8_t *d_status, void *stream);
+/* The same with every array on the host: n == 1 runs where airice_scalar_mode says (the calling
+ * thread, or the kernel through the one-query slot); n > 1 copies, launches and synchronises. */
+int airice_iceair_host(const double *model3, const double *z0, const double *x1, const double *h,
+                       size_t n, double *out, size_t ld, uint8_t *status);
+
+/* --- first arrivals between 3-D points (IceRayTracing::DirectRayTracer, IceRayTracing.cc:
+ * 2502-2612) -------------------------------------------------------------------------------------
+ * The first-arriving ray from each emitter (d_tx_x, d_tx_y, d_tx_z) to each antenna (d_rx_*), all
+ * in the ice, in three launches behind this one entry: icefirst_geom_kernel forms
+ * (z0, x1, z1) = (zT, sqrt(dx*dx + dy*dy), zR) per pair (no fused multiply-add, the correctly
+ * rounded root), iceray_kernel solves them (airice_iceray_launch's kernel), and
+ * icefirst_select_kernel makes the reference's choice: among D, Ra0 and Ra1 -- those whose receive
+ * angle is not -1000; never the reflected ray -- the first whose time*c is strictly the smallest,
+ * starting from min = 1e9.
+ * pairing: AIRICE_PAIRS_ELEMENTWISE (n_tx == n_rx, pair i = emitter i, antenna i) or
+ * AIRICE_PAIRS_CROSS (pair t*n_rx + r = emitter t, antenna r).  Every intermediate lives in
+ * d_work, work_bytes >= airice_icefirst_work_bytes(pairs) bytes of device memory.
+ * Value c of pair i lands at d_out[c*ld + i]: 0 launch angle, deg; 1 receive angle, deg;
+ * 2 geometric path, m; 3 time*c, m; 4 time, s; 5 the ray, with airice_icesol's codes (1 D, 3 Ra0,
+ * 4 Ra1; 0 none); 6 x1; 7 the solver's status byte (AIRICE_ICERAY_* bits; also d_status,
+ * nullable).  With no candidate columns 0-4 are -1000; a non-finite coordinate gives NaN there,
+ * ray 0 and AIRICE_ICERAY_NONFINITE.
+ * Stream-ordered, no device allocation; zero pairs is AIRICE_OK and nothing is launched; an unknown
+ * pairing, n_tx != n_rx with AIRICE_PAIRS_ELEMENTWISE, a null pointer, ld < pairs or a work_bytes
+ * too small is AIRICE_EINVAL before any device call, and airice_last_error() names the argument. */
+#define AIRICE_ICEFIRST_FIELDS 8
+#define AIRICE_ICEFIRST_LAUNCH_ANGLE 0
+#define AIRICE_ICEFIRST_RECEIVE_ANGLE 1
+#define AIRICE_ICEFIRST_PATH 2
+#define AIRICE_ICEFIRST_TIME_C 3
+#define AIRICE_ICEFIRST_TIME 4
+#define AIRICE_ICEFIRST_RAY_TYPE 5
+#define AIRICE_ICEFIRST_X1 6
+#define AIRICE_ICEFIRST_STATUS 7
+#define AIRICE_PAIRS_ELEMENTWISE 0
+#define AIRICE_PAIRS_CROSS 1
+size_t airice_icefirst_work_bytes(size_t n_pairs);
+int airice_icefirst_launch(const double *model3, const double *d_tx_x, const double *d_tx_y,
+                           const double *d_tx_z, size_t n_tx, const double *d_rx_x,
+                           const double *d_rx_y, const double *d_rx_z, size_t n_rx, int pairing,
+                           void *d_work, size_t work_bytes, double *d_out, size_t ld,
+                           uint8_t *d_status, void *stream);
+/* The last of the three launches on its own, for a caller that holds the solver's rows already:
+ * the choice over d_rays, the 32 columns airice_iceray_launch wrote (stride ld_rays), with d_x1
+ * passed through to column 6.  ONE launch of icefirst_select_kernel, stream-ordered, no device
+ * allocation; n == 0 is AIRICE_OK; a null d_rays, d_x1 or d_out, ld_rays < n or ld < n is
+ * AIRICE_EINVAL before any device call. */
+int airice_icefirst_select_launch(const double *d_rays, size_t ld_rays, const double *d_x1,
+                                  size_t n, double *d_out, size_t ld, uint8_t *d_status,
+                                  void *stream);
+/* The same choice over host rows, on the calling thread; no GPU. */
+int airice_icefirst_select_host(const double *rays, size_t ld_rays, const double *x1, size_t n,
+                                double *out, size_t ld, uint8_t *status);
+/* The same with every array on the host and no work buffer: one pair runs where airice_scalar_mode
+ * says (the calling thread, or the three kernels through the one-query slot); more are copied,
+ * launched and synchronised. */
+int airice_icefirst_host(const double *model3, const double *tx_x, const double *tx_y,
+                         const double *tx_z, size_t n_tx, const double *rx_x, const double *rx_y,
+                         const double *rx_z, size_t n_rx, int pairing, double *out, size_t ld,
+                         uint8_t *status);
+
 /* --- the two rays a receiver sees (IceRayTracing::GetRayTracingSolutions, IceRayTracing.cc:
  * 2907-3210) and their focusing factors (GetFocusingFactor, .cc:3218-3293) ----------------------
  * For n pairs in ONE launch of icesol_kernel, one pair per lane, over the rows airice_iceray_launch
@@ -790,7 +888,9 @@ int airice_table_load(const char *path, const airice_medium *expect, float *h_ta
  * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
  * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
  * (airice_icetab_lookup_launch), "icepath_consts_kernel" and "icepath_kernel" (the two kernels of
- * airice_icepath_launch), "icesol_spectrum_kernel" (airice_icesol_spectrum_launch).
+ * airice_icepath_launch), "icesol_spectrum_kernel" (airice_icesol_spectrum_launch),
+ * "iceair_kernel" (airice_iceair_launch), "icefirst_geom_kernel" and "icefirst_select_kernel"
+ * (the two kernels airice_icefirst_launch puts around "iceray_kernel").
  * airice_kernel_time waits for the recorded pairs
  * and returns their summed duration and count; reset != 0 clears them. */
 int airice_kernel_timing(int on);
@@ -809,7 +909,9 @@ int airice_kernel_time(const char *name, double *total_ms, int64_t *launches, in
  * (airice_iceray_launch), "icesol_kernel" (airice_icesol_launch), "icetab_points_kernel",
  * "icetab_pack_kernel" (airice_icetab_build_launch), "icetab_lookup_kernel"
  * (airice_icetab_lookup_launch), "icepath_consts_kernel", "icepath_kernel"
- * (airice_icepath_launch), "icesol_spectrum_kernel" (airice_icesol_spectrum_launch).
+ * (airice_icepath_launch), "icesol_spectrum_kernel" (airice_icesol_spectrum_launch),
+ * "iceair_kernel" (airice_iceair_launch), "icefirst_geom_kernel" and "icefirst_select_kernel"
+ * (airice_icefirst_launch, whose solve counts as "iceray_kernel").
  * AIRICE_LAUNCH_REPORT=1 in the environment prints every count to stderr when the library
  * unloads. */
 int airice_launch_count(const char *name, int64_t *count, int reset);
