@@ -5,14 +5,14 @@ A from-scratch HIP implementation of the uzairlatif90/AirIceRayTracing hot path
 the pythonwrapper ``Py_TraceIceToAir`` surface) behind a C-ABI (``include/airice.h``,
 ``libairice.so``).  See DESIGN.md.
 """
-from ._lib import (AirIceLibraryError, Grid, LOOKUP_FALLBACK, LOOKUP_UNPINNED, LookupTable,
+from ._lib import (AirIceLibraryError, Firn, Grid, LOOKUP_FALLBACK, LOOKUP_UNPINNED, LookupTable,
                    Medium, VARIANT_MULTIRAY, VARIANT_PYWRAPPER, build, default_atmosphere_path,
                    lib, load_medium)
 from .solver import (AirIceSolver, AntennaTables, IceTables, dedupe_depths, icetab_grid,
                      icetab_grid_init, make_grid)
 
 __all__ = [
-    "AirIceLibraryError", "AirIceSolver", "AntennaTables", "Grid", "IceTables", "LOOKUP_FALLBACK", "LOOKUP_UNPINNED",
+    "AirIceLibraryError", "AirIceSolver", "AntennaTables", "Firn", "Grid", "IceTables", "LOOKUP_FALLBACK", "LOOKUP_UNPINNED",
     "LookupTable", "Medium", "VARIANT_MULTIRAY",
     "VARIANT_PYWRAPPER", "build", "dedupe_depths", "default_atmosphere_path", "icetab_grid", "icetab_grid_init", "lib",
     "load_medium", "make_grid",

@@ -87,6 +87,22 @@ class Grid(ctypes.Structure):
         return int(self.table_rows) * int(self.angle_steps)
 
 
+class Firn(ctypes.Structure):
+    """airice_firn (include/airice.h): the two-layer firn n(z) = A_ice + B[l] exp(-C[l] z), l = 0
+    down to boundary_m and 1 below it."""
+
+    _fields_ = [("boundary_m", ctypes.c_double), ("B", ctypes.c_double * 2),
+                ("C", ctypes.c_double * 2)]
+
+    SUMMIT_A_ICE = 1.775  # the A_ice that goes with summit()
+
+    @classmethod
+    def summit(cls) -> "Firn":
+        """AIRICE_FIRN_SUMMIT: the Greenland (Summit) firn; use it with A_ice = 1.775."""
+        return cls(14.9, (ctypes.c_double * 2)(-0.5019, -0.448023),
+                   (ctypes.c_double * 2)(0.03247, 0.02469))
+
+
 class LookupTable(ctypes.Structure):
     """airice_lookup_table (include/airice.h): one antenna's HBM-resident table + the grid
     globals the reference's lookup reads (MultiRayAirIceRefraction.cc:1035-1039)."""
@@ -228,7 +244,10 @@ EXPORTED_SYMBOLS = (
     "airice_last_error", "airice_version", "airice_atmosphere_load", "airice_atmosphere_parse",
     "airice_nz_air", "airice_nz_ice", "airice_grid_init", "airice_table_launch",
     "airice_table_launch_multi",
-    "airice_table_host", "airice_rays_launch", "airice_rays_host", "airice_scalar_mode", "airice_solve_launch", "airice_solve_host",
+    "airice_table_host", "airice_rays_launch", "airice_rays_host",
+    "airice_nz_firn", "airice_table_launch_firn", "airice_table_launch_multi_firn",
+    "airice_table_host_firn", "airice_rays_launch_firn", "airice_rays_host_firn",
+    "airice_scalar_mode", "airice_solve_launch", "airice_solve_host",
     "airice_hdtip_launch", "airice_table_lookup_launch",
     "airice_table_lookup_multi_work_bytes", "airice_table_lookup_launch_multi", "airice_lookup_pack", "airice_lookup_pack_floats", "airice_single_ray_plan",
     "airice_single_ray_launch", "airice_single_ray_host", "airice_ray_paths_plan",
@@ -288,7 +307,7 @@ def lib() -> ctypes.CDLL:
     except OSError as e:  # pragma: no cover - depends on the box
         raise AirIceLibraryError(f"cannot load {LIB_PATH}: {e}") from e
     D, I, P, S = ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
-    M, G = ctypes.POINTER(Medium), ctypes.POINTER(Grid)
+    M, G, F = ctypes.POINTER(Medium), ctypes.POINTER(Grid), ctypes.POINTER(Firn)
     sig = {
         "airice_last_error": ([], ctypes.c_char_p),
         "airice_version": ([], ctypes.c_char_p),
@@ -302,6 +321,12 @@ def lib() -> ctypes.CDLL:
         "airice_table_launch_multi": ([M, G, ctypes.c_int32, P, P, P], I),
         "airice_rays_launch": ([M, P, P, D, D, ctypes.c_int32, S, P, S, P], I),
         "airice_rays_host": ([M, P, P, D, D, ctypes.c_int32, S, P, S], I),
+        "airice_nz_firn": ([M, F, D], D),
+        "airice_table_launch_firn": ([M, F, G, ctypes.c_int32, ctypes.c_int32, P, P, S, P], I),
+        "airice_table_host_firn": ([M, F, G, ctypes.c_int32, ctypes.c_int32, P, P, S], I),
+        "airice_table_launch_multi_firn": ([M, F, G, ctypes.c_int32, P, P, P], I),
+        "airice_rays_launch_firn": ([M, F, P, P, D, D, ctypes.c_int32, S, P, S, P], I),
+        "airice_rays_host_firn": ([M, F, P, P, D, D, ctypes.c_int32, S, P, S], I),
         "airice_scalar_mode": ([I], I),
         "airice_solve_launch": ([M, I, D, P, P, P, P, S, P, S, P, P], I),
         "airice_solve_host": ([M, I, D, P, P, P, P, S, P, S, P], I),

@@ -106,6 +106,17 @@ struct IceConsts {
   double n_ratio;              // n_air_ice / n_ice0 (IEEE quotient, folded on the host)
 };
 
+// The lower leg of a two-layer firn: the ice segment of IceConsts then ends at the
+// layer boundary (the antenna depth clipped to it) in the upper layer's model, and this is the
+// segment below it -- boundary -> antenna, both ends in the lower layer's model.  Passed beside
+// IceConsts to the layered kernels only.
+struct FirnLeg {
+  SegConst seg;    // lower model: boundary -> antenna
+  double ratio_b;  // n_up(boundary) / n_low(boundary): the sine's step across the index step
+  int below;       // the antenna lies below the boundary (else seg is unused)
+  int pad_;
+};
+
 __host__ __device__ inline SegConst make_segconst(const Endpoint& T, const Endpoint& R) {
   const double speedc = 299792458.0;
   SegConst s;
@@ -499,6 +510,14 @@ __device__ __forceinline__ void formed_here_s(const SegConst& S, double a, doubl
   __asm__ volatile("" ::"s"(S.Tn), "s"(S.Ty2), "s"(S.TAy), "s"(S.Rn), "s"(S.Ry2), "s"(S.RAy),
                    "s"(S.ratio), "s"(S.invC), "s"(S.invCc), "s"(S.dCx), "s"(S.dACx), "s"(a),
                    "s"(b), "s"(c), "s"(d), "s"(p));
+}
+
+// the same for the lower leg of a layered firn
+__device__ __forceinline__ void formed_here_s(const FirnLeg& F) {
+  const SegConst& S = F.seg;
+  __asm__ volatile("" ::"s"(S.Tn), "s"(S.Ty2), "s"(S.TAy), "s"(S.Rn), "s"(S.Ry2), "s"(S.RAy),
+                   "s"(S.ratio), "s"(S.invC), "s"(S.invCc), "s"(S.dCx), "s"(S.dACx),
+                   "s"(F.ratio_b));
 }
 
 __device__ __forceinline__ void signal_done(const Signal& s) {

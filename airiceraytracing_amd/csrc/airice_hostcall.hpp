@@ -89,6 +89,9 @@ inline int bad_lookup_table(const char* who, const airice_lookup_table* t, int i
   return AIRICE_OK;
 }
 
+// The firn of a *_firn entry point: non-null, every field finite, boundary_m > 0, C[l] > 0.
+inline int bad_firn(const char* who, const airice_firn* f) { return firn_check(who, f); }
+
 // model3, or IceRayTracing's default {A, B, C} (airice_iceray.hpp) when it is null.
 inline const double* ice_model_or_default(const double* model3) {
   static const double kDefault[3] = {iceray::kDefaultModel.A, iceray::kDefaultModel.B,

@@ -30,6 +30,7 @@ inline int launch_ok() { return hipGetLastError() == hipSuccess ? AIRICE_OK : AI
 // (airice_solve.hip).
 AIRICE_LOCAL int bisect_exact();
 
+// The host folds (airice_fold.cpp).
 // Kernel-argument medium for one variant (pi) built from the parsed medium; the
 // layer-boundary endpoints are evaluated here, on the host, once.
 int build_dev_medium(const airice_medium* m, int variant, DevMedium* out);
@@ -38,11 +39,29 @@ void build_ice_consts(const DevMedium& M, double ice_h, double rx_depth, IceCons
 
 Endpoint host_air_endpoint(const DevMedium& M, double x);
 Endpoint host_ice_endpoint(const DevMedium& M, double x);
+// Two-layer firn (airice_firn).  firn_check: the argument check of the *_firn entry
+// points (sets the error, AIRICE_EINVAL).  The upper leg is the one-layer fold of
+// firn_layer_medium(m, f, 0) with the antenna depth clipped to the boundary (firn_clip_depth);
+// build_firn_leg folds the lower leg from that medium's DevMedium and the unclipped depth
+// rx_depth (m, >= 0 in the ice).  rays_host_firn: rays_host's loop over the layered ray.
+AIRICE_LOCAL int firn_check(const char* who, const airice_firn* f);
+AIRICE_LOCAL airice_medium firn_layer_medium(const airice_medium& m, const airice_firn& f,
+                                             int layer);
+AIRICE_LOCAL double firn_clip_depth(const airice_firn& f, double rx_depth);
+AIRICE_LOCAL void build_firn_leg(const DevMedium& M, const airice_firn& f, double rx_depth,
+                                 FirnLeg* out);
+AIRICE_LOCAL void rays_host_firn(const DevMedium& M, const IceConsts& I, const FirnLeg& F,
+                                 const double* launch, const double* txh, int in_ice, size_t n,
+                                 double* out, size_t ld);
 
+// F / Fh (nullable, here and in launch_rays / rays_host): the lower leg of a two-layer firn
+// (build_firn_leg); M and I then describe the upper layer and the layered kernels run.
 int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, int row_begin,
-                 int row_count, float* d_table, double* d_full, size_t ld, hipStream_t st);
+                 int row_count, float* d_table, double* d_full, size_t ld, hipStream_t st,
+                 const FirnLeg* F = nullptr);
 int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_grid* grids, int n,
-                       float* const* tables, const size_t* lds, hipStream_t st);
+                       float* const* tables, const size_t* lds, hipStream_t st,
+                       const FirnLeg* Fh = nullptr);
 // entries of the table launch's per-grid caches (airice_table_cache_stats)
 void table_cache_stats(int out[6]);
 // the air-record cache of the table launch (airice_air_cache_stats / airice_air_cache_limits):
@@ -50,9 +69,10 @@ void table_cache_stats(int out[6]);
 void air_cache_stats(long long out[6]);
 int air_cache_limits(long long entry_bytes, long long total_bytes);
 int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
-                int in_ice, size_t n, double* out, size_t ld, hipStream_t st);
+                int in_ice, size_t n, double* out, size_t ld, hipStream_t st,
+                const FirnLeg* F = nullptr);
 void rays_host(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
-               int in_ice, size_t n, double* out, size_t ld);
+               int in_ice, size_t n, double* out, size_t ld, const FirnLeg* F = nullptr);
 // one query of the minimizer entry points on the host (airice_solve.hip: solve_one_host_t)
 int solve_host_one(const DevMedium& M, const IceConsts& I, int variant, const double* in,
                    bool has_thr, double* out, uint8_t* status);

@@ -5,7 +5,9 @@
 // the row's constants RowConst and the start sine) and ray_ice_part (the segment in the ice, the
 // receive angle, the Fresnel coefficients, the 18 outputs); ray_solution_row is the one followed
 // by the other, ray_solution the per-lane form with its own row constants.  The table and ray
-// kernels (airice_table.hip) and the host route rays_host are written over them.  The minimizer's
+// kernels (airice_table.hip) and the host route rays_host are written over them.  The ice part in
+// a two-layer firn (the reference's TransitionBoundary != 0 model) is ray_ice_part_firn, DESIGN.md
+// §14.  The minimizer's
 // stage 2 (airice_minimizer.hpp) takes stop_of, fresnel_from_sine and sin_start from here and
 // nothing else.
 #pragma once
@@ -251,31 +253,89 @@ __host__ __device__ __forceinline__ void ray_ice_part(const DevMedium& M, const 
   d[17] = geo_ice;
 }
 
+// The ice part in a two-layer firn: M and I describe the upper layer, I.iceseg ends
+// at the layer boundary when the antenna lies below it (F.below), and F.seg is the leg from the
+// boundary to the antenna in the lower layer's model.  L = n sin(theta) is conserved across the
+// index step, so the sine entering the lower leg is F.ratio_b times the upper leg's output sine.
+// d[4], d[7], d[10], d[17] are the two legs' sums, d[13] is the angle at the antenna; the Fresnel
+// coefficients stay those of the surface.  With F.below == 0 these are ray_ice_part's operations.
+template <bool FRESNEL = true>
+__host__ __device__ __forceinline__ void ray_ice_part_firn(const DevMedium& M, const IceConsts& I,
+                                                           const FirnLeg& F, double H, double theta,
+                                                           bool in_ice, double vinc, double thd_air,
+                                                           double t_air, double geo_air, double inc,
+                                                           double* d, const double* tab) {
+  double thd_ice = 0.0, t_ice = 0.0, geo_ice = 0.0, recv_ice = 0.0;
+  if (in_ice) {
+    const double A2i = M.A_ice * M.A_ice;
+    const double u = sin_asin(I.n_ratio * vinc);
+    double v2;
+    const Segment s = segment_const(I.iceseg, M.A_ice, A2i, u, false, v2, tab);
+    thd_ice += s.thd;
+    t_ice += s.t;
+    geo_ice += s.geo;
+    if (F.below != 0) {
+      const double ub = sin_asin(F.ratio_b * v2);
+      const Segment q = segment_const(F.seg, M.A_ice, A2i, ub, false, v2, tab);
+      thd_ice += q.thd;
+      t_ice += q.t;
+      geo_ice += q.geo;
+    }
+    recv_ice = k_asin(v2) * M.r2d;
+  }
+  double tS = 0.0, tP = 0.0;
+  if constexpr (FRESNEL) fresnel_from_sine(I.n_air_ice, I.n_ice0, I.n_ratio, vinc, tS, tP);
+  d[0] = 0;
+  d[1] = H;
+  d[2] = thd_air + thd_ice;
+  d[3] = thd_air;
+  d[4] = thd_ice;
+  d[5] = (t_ice + t_air) * kSpeedC;
+  d[6] = t_air * kSpeedC;
+  d[7] = t_ice * kSpeedC;
+  d[8] = (t_ice + t_air) * 1e9;
+  d[9] = t_air * 1e9;
+  d[10] = t_ice * 1e9;
+  d[11] = theta;
+  d[12] = inc;
+  d[13] = recv_ice;
+  d[14] = tS;
+  d[15] = tP;
+  d[16] = geo_air;
+  d[17] = geo_ice;
+}
+
 // want_inc: dummy[12] (the incidence angle on the ice, one asin) is not a table column
 // (.cc:2101-2111), so table launches without the double output skip it.
 // v_start: the sine of StartAngle, formed by the caller.
+// F: the lower leg of a layered firn (ray_ice_part_firn), nullptr in the one-layer model.
 template <bool A1 = false>
 __host__ __device__ __forceinline__ void ray_solution_row(const DevMedium& M, const IceConsts& I,
                                                  const RowConst& rc, double theta, bool in_ice,
                                                  double* d, bool want_inc,
                                                  const double* tab = &kLogTable[0][0],
                                                  int top_hi = -1,
-                                                 const double* v_start = nullptr) {
+                                                 const double* v_start = nullptr,
+                                                 const FirnLeg* F = nullptr) {
   // sine of StartAngle (.cc:1863); v_start: the same value, formed by the caller
   const double v = v_start != nullptr ? *v_start : sin_start((180 - theta) * M.d2r);
   const AirPart a = ray_air_part<A1>(M, I, rc, v, tab, top_hi);
   // IncidentAngleonIce = last layer's receive angle; 0 when no air layer (.cc:1832, 1881)
   double inc = 0.0;
   if (want_inc) inc = a.any ? k_asin(a.v) * M.r2d : 0.0;
-  ray_ice_part(M, I, rc.H, theta, in_ice, a.vinc, a.thd_air, a.t_air, a.geo_air, inc, d, tab);
+  if (F != nullptr)
+    ray_ice_part_firn(M, I, *F, rc.H, theta, in_ice, a.vinc, a.thd_air, a.t_air, a.geo_air, inc, d,
+                      tab);
+  else
+    ray_ice_part(M, I, rc.H, theta, in_ice, a.vinc, a.thd_air, a.t_air, a.geo_air, inc, d, tab);
 }
 
 // Per-lane form (rays, minimizer evaluations): the row constants of its own Tx height.
 __host__ __device__ __forceinline__ void ray_solution(const DevMedium& M, const IceConsts& I, double theta,
                                              double H, bool in_ice, double* d,
-                                             bool want_inc = true) {
+                                             bool want_inc = true, const FirnLeg* F = nullptr) {
   const RowConst rc = row_const(M, I, H);
-  ray_solution_row(M, I, rc, theta, in_ice, d, want_inc);
+  ray_solution_row(M, I, rc, theta, in_ice, d, want_inc, &kLogTable[0][0], -1, nullptr, F);
 }
 
 }  // namespace airice

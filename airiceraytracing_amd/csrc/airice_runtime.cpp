@@ -23,108 +23,6 @@
 
 namespace airice {
 
-static int host_air_layer(const DevMedium& M, double zabs) {
-  int which = 0;
-  for (int l = 0; l < M.ml - 1; ++l) {
-    if (zabs < M.atm[l + 1] && zabs >= M.atm[l]) {
-      which = l;
-      break;
-    }
-  }
-  if (zabs >= M.atm[M.ml - 1]) which = M.ml - 1;
-  return which;
-}
-
-Endpoint host_air_endpoint(const DevMedium& M, double x) {
-  const double zabs = std::fabs(x);
-  const int l = host_air_layer(M, zabs);
-  const double C = M.negC[l];
-  const double e_abs = std::exp(C * zabs);
-  const double e_x = x >= 0.0 ? e_abs : std::exp(C * x);
-  return make_endpoint(M.A_air, M.B[l], C, x, e_abs, e_x);
-}
-
-Endpoint host_ice_endpoint(const DevMedium& M, double x) {
-  const double zabs = std::fabs(x);
-  const double e_abs = std::exp(M.negC_ice * zabs);
-  const double e_x = x >= 0.0 ? e_abs : std::exp(M.negC_ice * x);
-  return make_endpoint(M.A_ice, M.B_ice, M.negC_ice, x, e_abs, e_x);
-}
-
-int build_dev_medium(const airice_medium* m, int variant, DevMedium* out) {
-  if (m == nullptr || out == nullptr) {
-    set_error("null medium");
-    return AIRICE_EINVAL;
-  }
-  if (m->max_layers < 1 || m->max_layers > kMaxLayers) {
-    set_error("medium not initialised (max_layers=%d)", m->max_layers);
-    return AIRICE_EINVAL;
-  }
-  DevMedium& M = *out;
-  std::memset(&M, 0, sizeof(M));
-  const double pi = variant_pi(variant);
-  for (int i = 0; i < 5; ++i) {
-    M.atm[i] = m->atmlay_cm[i] / 100;
-    M.B[i] = m->B_air[i];
-    M.negC[i] = -m->C_air[i];
-  }
-  M.A_air = m->A_air;
-  M.A_ice = m->A_ice;
-  M.B_ice = m->B_ice;
-  M.negC_ice = -m->C_ice;
-  M.d2r = pi / 180.0;
-  M.r2d = 180 / pi;
-  M.ml = m->max_layers;
-  if (variant == AIRICE_VARIANT_PYWRAPPER && m->constant_air_index) {
-    // UseConstantRefractiveIndex (pythonwrapper AirIceRayTracing.cc:173-238): GetB_air = 0,
-    // GetC_air = 1e-9 in every layer; Getnz_air = A_const, which A_air + 0*exp() reproduces
-    // exactly while A_const == A_air (both 1.00, .h:69-72)
-    if (m->A_const != m->A_air) {
-      set_error("constant air index: A_const (%g) != A_air (%g) is not supported", m->A_const,
-                m->A_air);
-      return AIRICE_EINVAL;
-    }
-    for (int i = 0; i < 5; ++i) {
-      M.B[i] = 0;
-      M.negC[i] = -1e-9;
-    }
-    M.const_air = 1;
-  }
-  for (int l = 0; l < kMaxLayers; ++l) {
-    M.start[l] = host_air_endpoint(M, M.atm[l + 1] - 0.00001);
-    M.stop[l] = host_air_endpoint(M, M.atm[l]);
-  }
-  return AIRICE_OK;
-}
-
-void build_ice_consts(const DevMedium& M, double ice_h, double rx_depth, IceConsts* out) {
-  std::memset(out, 0, sizeof(*out));
-  out->ice_h = ice_h;
-  out->ice_air = host_air_endpoint(M, ice_h);
-  out->ice0 = host_ice_endpoint(M, 0.0);
-  out->ice_rx = host_ice_endpoint(M, rx_depth);
-  out->n_air_ice = out->ice_air.n;
-  out->n_ice0 = out->ice0.n;
-  out->n_ratio = out->n_air_ice / out->n_ice0;
-  // lowest air layer: SkipLayersBelow scan (.cc:1815-1825)
-  int bot = 0;
-  for (int il = 0; il < M.ml; ++il) {
-    if (ice_h >= M.atm[il] && ice_h < M.atm[il + 1]) break;
-    ++bot;
-  }
-  out->bot = bot;
-  for (int l = 0; l < kMaxLayers; ++l) {
-    const Endpoint& T = M.start[l];
-    Endpoint R = (l == bot) ? out->ice_air : M.stop[l];
-    out->topend[l] = make_topend(R);
-    if (R.x == T.x) R = T;  // zero-length segment: the same function of the same x
-    out->lower[l] = make_segconst(T, R);
-  }
-  Endpoint rx = out->ice_rx;
-  if (rx.x == out->ice0.x) rx = out->ice0;
-  out->iceseg = make_segconst(out->ice0, rx);
-}
-
 // ---- one-query calls on the host ---------------------------------------------------------
 // Where the one-query ray and ray-layer calls run (airice_scalar_mode): AIRICE_SCALAR_HOST (the
 // default) or AIRICE_SCALAR_DEVICE (the one-wave kernels through the scalar slot); the environment
@@ -528,9 +426,26 @@ extern "C" int airice_kernel_time(const char* name, double* total_ms, int64_t* l
 
 extern "C" {
 
+// The folds of a call in a two-layer firn (f checked by bad_firn): M and I from the upper layer's
+// medium with the antenna depth clipped to the boundary, the lower leg F, and whether the call
+// takes the layered kernels at all -- an antenna at or above the boundary or in the air takes the
+// one-layer kernels with M and I (*Fp = nullptr).
+static int firn_folds(const airice_medium& m, const airice_firn& f, double ice_h, double rx_depth,
+                      int in_ice, DevMedium* M, IceConsts* I, FirnLeg* F, const FirnLeg** Fp) {
+  const airice_medium up = firn_layer_medium(m, f, 0);
+  if (int rc = launch_folds(&up, AIRICE_VARIANT_MULTIRAY, ice_h, firn_clip_depth(f, rx_depth), M, I))
+    return rc;
+  build_firn_leg(*M, f, rx_depth, F);
+  *Fp = (in_ice != 0 && F->below != 0) ? F : nullptr;
+  return AIRICE_OK;
+}
+
 // The checks and folds of a table call; table: its (required) 11-column table, by name.
+// f (nullable): the call's firn, with F and Fp as firn_folds.
 static int table_prepare(const airice_medium* m, const airice_grid* g, int32_t row_begin,
-                         int32_t row_count, NamedArg table, size_t ld, DevMedium* M, IceConsts* I) {
+                         int32_t row_count, NamedArg table, size_t ld, DevMedium* M, IceConsts* I,
+                         const airice_firn* f = nullptr, FirnLeg* F = nullptr,
+                         const FirnLeg** Fp = nullptr) {
   if (g == nullptr || row_begin < 0 || row_count < 0 ||
       (int64_t)row_begin + row_count > g->height_steps) {
     set_error("row range [%d,+%d) outside grid of %d rows", row_begin, row_count,
@@ -540,6 +455,8 @@ static int table_prepare(const airice_medium* m, const airice_grid* g, int32_t r
   if (int rc = short_stride("table", "ld", ld, (size_t)row_count * (size_t)g->angle_steps))
     return rc;
   if (int rc = null_argument("table", {{"m", m}, table})) return rc;
+  if (f != nullptr)
+    return firn_folds(*m, *f, g->stop_height, -g->depth_m, g->in_ice, M, I, F, Fp);
   return launch_folds(m, AIRICE_VARIANT_MULTIRAY, g->stop_height, -g->depth_m, M, I);
 }
 
@@ -548,21 +465,39 @@ static int32_t kept_rows(const airice_grid* g, int32_t row_begin, int32_t row_co
   return std::max<int32_t>(0, std::min<int32_t>(row_count, g->table_rows - row_begin));
 }
 
-int airice_table_launch(const airice_medium* m, const airice_grid* g, int32_t row_begin,
-                        int32_t row_count, float* d_table, double* d_full, size_t ld,
-                        void* stream) {
+// The table and ray entry points, one body each for the one-layer call (f == nullptr) and its
+// *_firn namesake.
+static int table_launch(const airice_medium* m, const airice_firn* f, const airice_grid* g,
+                        int32_t row_begin, int32_t row_count, float* d_table, double* d_full,
+                        size_t ld, void* stream) {
   DevMedium M;
   IceConsts I;
-  int rc = table_prepare(m, g, row_begin, row_count, {"d_table", d_table}, ld, &M, &I);
+  FirnLeg F;
+  const FirnLeg* Fp = nullptr;
+  int rc = table_prepare(m, g, row_begin, row_count, {"d_table", d_table}, ld, &M, &I, f, &F, &Fp);
   if (rc) return rc;
   rc = launch_table(M, I, g, row_begin, kept_rows(g, row_begin, row_count), d_table, d_full, ld,
-                    (hipStream_t)stream);
+                    (hipStream_t)stream, Fp);
   if (rc) set_error("table launch failed: %s", hipGetErrorString(hipGetLastError()));
   return rc;
 }
 
-int airice_table_launch_multi(const airice_medium* m, const airice_grid* grids, int32_t n_grids,
-                              float* const* d_tables, const size_t* lds, void* stream) {
+int airice_table_launch(const airice_medium* m, const airice_grid* g, int32_t row_begin,
+                        int32_t row_count, float* d_table, double* d_full, size_t ld,
+                        void* stream) {
+  return table_launch(m, nullptr, g, row_begin, row_count, d_table, d_full, ld, stream);
+}
+
+int airice_table_launch_firn(const airice_medium* m, const airice_firn* f, const airice_grid* g,
+                             int32_t row_begin, int32_t row_count, float* d_table, double* d_full,
+                             size_t ld, void* stream) {
+  if (int rc = bad_firn("table", f)) return rc;
+  return table_launch(m, f, g, row_begin, row_count, d_table, d_full, ld, stream);
+}
+
+static int table_launch_multi(const airice_medium* m, const airice_firn* f,
+                              const airice_grid* grids, int32_t n_grids, float* const* d_tables,
+                              const size_t* lds, void* stream) {
   if (n_grids < 0) {
     set_error("table multi: n_grids = %d", n_grids);
     return AIRICE_EINVAL;
@@ -572,28 +507,53 @@ int airice_table_launch_multi(const airice_medium* m, const airice_grid* grids, 
                                              {"lds", lds}}))
     return rc;
   DevMedium M;
-  int rc = build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M);
+  const airice_medium up = f != nullptr ? firn_layer_medium(*m, *f, 0) : *m;
+  int rc = build_dev_medium(&up, AIRICE_VARIANT_MULTIRAY, &M);
   if (rc) return rc;
   std::vector<IceConsts> I(n_grids);
+  std::vector<FirnLeg> F(f != nullptr ? n_grids : 0);
+  bool layered = false;  // an antenna below the boundary: the layered kernel
   for (int a = 0; a < n_grids; ++a) {
     const airice_grid& g = grids[a];
     if (g.angle_steps != grids[0].angle_steps || g.angle_steps < 1 || d_tables[a] == nullptr) {
       set_error("multi-antenna launch: antenna %d has another angle grid or no table", a);
       return AIRICE_EINVAL;
     }
-    build_ice_consts(M, g.stop_height, -g.depth_m, &I[a]);
+    if (f == nullptr) {
+      build_ice_consts(M, g.stop_height, -g.depth_m, &I[a]);
+      continue;
+    }
+    build_ice_consts(M, g.stop_height, firn_clip_depth(*f, -g.depth_m), &I[a]);
+    build_firn_leg(M, *f, -g.depth_m, &F[a]);
+    layered = layered || (g.in_ice != 0 && F[a].below != 0);
   }
-  rc = launch_table_multi(M, I.data(), grids, n_grids, d_tables, lds, (hipStream_t)stream);
+  rc = launch_table_multi(M, I.data(), grids, n_grids, d_tables, lds, (hipStream_t)stream,
+                          layered ? F.data() : nullptr);
   if (rc && rc != AIRICE_EINVAL)
     set_error("multi-antenna table launch failed: %s", hipGetErrorString(hipGetLastError()));
   return rc;
 }
 
-int airice_table_host(const airice_medium* m, const airice_grid* g, int32_t row_begin,
-                      int32_t row_count, float* h_table, double* h_full, size_t ld) {
+int airice_table_launch_multi(const airice_medium* m, const airice_grid* grids, int32_t n_grids,
+                              float* const* d_tables, const size_t* lds, void* stream) {
+  return table_launch_multi(m, nullptr, grids, n_grids, d_tables, lds, stream);
+}
+
+int airice_table_launch_multi_firn(const airice_medium* m, const airice_firn* f,
+                                   const airice_grid* grids, int32_t n_grids,
+                                   float* const* d_tables, const size_t* lds, void* stream) {
+  if (int rc = bad_firn("table multi", f)) return rc;
+  return table_launch_multi(m, f, grids, n_grids, d_tables, lds, stream);
+}
+
+static int table_host(const airice_medium* m, const airice_firn* f, const airice_grid* g,
+                      int32_t row_begin, int32_t row_count, float* h_table, double* h_full,
+                      size_t ld) {
   DevMedium M;
   IceConsts I;
-  int rc = table_prepare(m, g, row_begin, row_count, {"h_table", h_table}, ld, &M, &I);
+  FirnLeg F;
+  const FirnLeg* Fp = nullptr;
+  int rc = table_prepare(m, g, row_begin, row_count, {"h_table", h_table}, ld, &M, &I, f, &F, &Fp);
   if (rc) return rc;
   DevBuffer dt, df;
   HIP_TRY(dt.alloc(sizeof(float) * 11 * ld));
@@ -604,12 +564,24 @@ int airice_table_host(const airice_medium* m, const airice_grid* g, int32_t row_
     if (h_full) HIP_TRY(hipMemset(df.p, 0xFF, sizeof(double) * 18 * ld));
   }
   rc = launch_table(M, I, g, row_begin, rows, static_cast<float*>(dt.p),
-                    static_cast<double*>(df.p), ld, nullptr);
+                    static_cast<double*>(df.p), ld, nullptr, Fp);
   if (rc == AIRICE_OK) {
     HIP_TRY(hipMemcpy(h_table, dt.p, sizeof(float) * 11 * ld, hipMemcpyDeviceToHost));
     if (h_full) HIP_TRY(hipMemcpy(h_full, df.p, sizeof(double) * 18 * ld, hipMemcpyDeviceToHost));
   }
   return rc;
+}
+
+int airice_table_host(const airice_medium* m, const airice_grid* g, int32_t row_begin,
+                      int32_t row_count, float* h_table, double* h_full, size_t ld) {
+  return table_host(m, nullptr, g, row_begin, row_count, h_table, h_full, ld);
+}
+
+int airice_table_host_firn(const airice_medium* m, const airice_firn* f, const airice_grid* g,
+                           int32_t row_begin, int32_t row_count, float* h_table, double* h_full,
+                           size_t ld) {
+  if (int rc = bad_firn("table", f)) return rc;
+  return table_host(m, f, g, row_begin, row_count, h_table, h_full, ld);
 }
 
 int airice_rays_host(const airice_medium* m, const double* launch_deg, const double* txh,
@@ -623,6 +595,23 @@ int airice_rays_host(const airice_medium* m, const double* launch_deg, const dou
   const IceConsts* I = nullptr;
   if (int rc = airice::folded_ice(m, AIRICE_VARIANT_MULTIRAY, ice_h_m, -depth_m, &M, &I)) return rc;
   airice::rays_host(*M, *I, launch_deg, txh, in_ice, n, out, ld);
+  return AIRICE_OK;
+}
+
+int airice_rays_host_firn(const airice_medium* m, const airice_firn* f, const double* launch_deg,
+                          const double* txh, double ice_h_m, double depth_m, int32_t in_ice,
+                          size_t n, double* out, size_t ld) {
+  if (int rc = bad_firn("rays", f)) return rc;
+  if (int rc = null_argument("rays", {{"m", m}, {"out", out}})) return rc;
+  if (n > 0)
+    if (int rc = null_argument("rays", {{"launch_deg", launch_deg}, {"txh", txh}})) return rc;
+  if (int rc = short_stride("rays", "ld", ld, n)) return rc;
+  DevMedium M;
+  IceConsts I;
+  FirnLeg F;
+  const FirnLeg* Fp = nullptr;
+  if (int rc = firn_folds(*m, *f, ice_h_m, -depth_m, in_ice, &M, &I, &F, &Fp)) return rc;
+  airice::rays_host(M, I, launch_deg, txh, in_ice, n, out, ld, Fp);
   return AIRICE_OK;
 }
 
@@ -640,6 +629,24 @@ int airice_rays_launch(const airice_medium* m, const double* d_launch, const dou
   IceConsts I;
   if (int rc = launch_folds(m, AIRICE_VARIANT_MULTIRAY, ice_h_m, -depth_m, &M, &I)) return rc;
   return launch_rays(M, I, d_launch, d_txh, in_ice, n, d_out, ld, (hipStream_t)stream);
+}
+
+int airice_rays_launch_firn(const airice_medium* m, const airice_firn* f, const double* d_launch,
+                            const double* d_txh, double ice_h_m, double depth_m, int32_t in_ice,
+                            size_t n, double* d_out, size_t ld, void* stream) {
+  if (int rc = bad_firn("rays", f)) return rc;
+  if (int rc = null_argument("rays", {{"m", m}})) return rc;
+  if (n > 0)
+    if (int rc = null_argument("rays", {{"d_launch", d_launch}, {"d_txh", d_txh},
+                                        {"d_out", d_out}}))
+      return rc;
+  if (int rc = short_stride("rays", "ld", ld, n)) return rc;
+  DevMedium M;
+  IceConsts I;
+  FirnLeg F;
+  const FirnLeg* Fp = nullptr;
+  if (int rc = firn_folds(*m, *f, ice_h_m, -depth_m, in_ice, &M, &I, &F, &Fp)) return rc;
+  return launch_rays(M, I, d_launch, d_txh, in_ice, n, d_out, ld, (hipStream_t)stream, Fp);
 }
 
 int airice_solve_launch(const airice_medium* m, int variant, double ice_h_m, const double* d_txh,
@@ -844,6 +851,12 @@ double airice_nz_air(const airice_medium* m, double z) {
   DevMedium M;
   if (build_dev_medium(m, AIRICE_VARIANT_MULTIRAY, &M) != AIRICE_OK) return NAN;
   return host_air_endpoint(M, std::fabs(z)).n;
+}
+
+double airice_nz_firn(const airice_medium* m, const airice_firn* f, double z) {
+  if (m == nullptr || f == nullptr) return std::nan("");
+  const int l = std::fabs(z) <= f->boundary_m ? 0 : 1;
+  return m->A_ice + f->B[l] * std::exp(-f->C[l] * std::fabs(z));
 }
 
 double airice_nz_ice(const airice_medium* m, double z) {

@@ -13,6 +13,8 @@
 //                         (ray_ice_part) only.
 //  rays_kernel          : the same ray for arbitrary (angle, height) lists.
 //  scalar_ray_kernel    : one ray (n = 1) spread over a wave.
+//  table_firn_kernel, table_multi_firn_kernel, rays_firn_kernel : the table (cold and warm), the
+//                         multi-antenna table and the rays in a two-layer firn (ray_ice_part_firn).
 // Launchers: launch_table, launch_table_multi, launch_rays; rays_host is the one-query host route.
 // The caches (row_cache, angle_cache, air_cache: GridCache; the multi-antenna launch's constant
 // sets: ConstSetCache) have their policy in airice_gridcache.hpp.
@@ -165,7 +167,8 @@ template <bool A1, bool SC1>
 __device__ __forceinline__ void table_ray(const DevMedium& M, const IceConsts& I,
                                           const TableArgs& G, const RowConst& rc, int r, int k,
                                           float* __restrict__ table, double* __restrict__ full,
-                                          const double* tab, int top_hi) {
+                                          const double* tab, int top_hi,
+                                          const FirnLeg* F = nullptr) {
   const int iang = k - r * G.asteps;
   const double th = table_angle(G, iang);
   double d[18];
@@ -176,7 +179,7 @@ __device__ __forceinline__ void table_ray(const DevMedium& M, const IceConsts& I
     vs = G.vs[iang];
   else
     vs = sin_start((180 - th) * M.d2r);
-  ray_solution_row<A1>(M, I, rc, th, G.in_ice != 0, d, full != nullptr, tab, top_hi, &vs);
+  ray_solution_row<A1>(M, I, rc, th, G.in_ice != 0, d, full != nullptr, tab, top_hi, &vs, F);
   const size_t ld = G.ld;
   table_columns<SC1>(table, ld, k, (float)d[1], (float)d[2], (float)d[7], (float)d[6],
                      (float)d[11], (float)d[3], (float)d[14], (float)d[15], (float)d[16],
@@ -222,17 +225,21 @@ __device__ __forceinline__ void table_ray_air(const DevMedium& M, const IceConst
 // zero radicands take it, none of them in a grid like cfg2.
 constexpr unsigned kWarmEarlyColumns = 0x1F9u;                          // 0, 3, 4, 5, 6, 7, 8
 constexpr unsigned kWarmLateColumns = kAllColumns & ~kWarmEarlyColumns;  // 1, 2, 9, 10
-template <bool SC1>
+template <bool SC1, bool FIRN = false>
 __device__ __forceinline__ void table_ray_warm(const DevMedium& M, const IceConsts& I,
                                                const TableArgs& G, int k, double H, double th,
                                                const double2 rd, const float4 rf,
-                                               float* __restrict__ table, const double* tab) {
+                                               float* __restrict__ table, const double* tab,
+                                               const FirnLeg* F = nullptr) {
   const double vinc = rd.x, thd_air = rd.y;
   table_columns<SC1, kWarmEarlyColumns>(table, G.ld, k, (float)H, 0.f, 0.f, rf.x, (float)th,
                                         (float)thd_air, rf.z, rf.w, rf.y, 0.f, 0.f);
   __builtin_amdgcn_sched_barrier(0);
   double d[18];
-  ray_ice_part<false>(M, I, H, th, G.in_ice != 0, vinc, thd_air, 0.0, 0.0, 0.0, d, tab);
+  if constexpr (FIRN)
+    ray_ice_part_firn<false>(M, I, *F, H, th, G.in_ice != 0, vinc, thd_air, 0.0, 0.0, 0.0, d, tab);
+  else
+    ray_ice_part<false>(M, I, H, th, G.in_ice != 0, vinc, thd_air, 0.0, 0.0, 0.0, d, tab);
   table_columns<SC1, kWarmLateColumns>(table, G.ld, k, 0.f, (float)d[2], (float)d[7], 0.f, 0.f,
                                        0.f, 0.f, 0.f, 0.f, (float)d[17], (float)d[13]);
 }
@@ -250,12 +257,15 @@ __device__ __forceinline__ void table_ray_warm(const DevMedium& M, const IceCons
 // MODE: kTableFull traces whole rays; kTableAir traces the air part only and writes the launch's
 // air record (no table); kTableWarm reads the air record and traces the ice part only -- it needs
 // neither the rows' constants (the Tx height comes from row_height) nor the start sines.
+// FIRN, F: the lower leg of a layered firn (the *_firn kernels); else F is nullptr and every use of
+// it folds away.
 enum { kTableFull = 0, kTableAir = 1, kTableWarm = 2 };
-template <bool TRACE, bool A1, bool SC1, int MODE = kTableFull>
+template <bool TRACE, bool A1, bool SC1, int MODE = kTableFull, bool FIRN = false>
 __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts& I,
                                             const TableArgs& G, float* __restrict__ table,
                                             double* __restrict__ full,
-                                            WaveTrace* __restrict__ trace, unsigned block) {
+                                            WaveTrace* __restrict__ trace, unsigned block,
+                                            const FirnLeg* F = nullptr) {
   constexpr int BS = kTableBlock;
   extern __shared__ __align__(16) unsigned char smem[];
   RowConst* rows = reinterpret_cast<RowConst*>(smem);
@@ -295,13 +305,14 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
     // reads (one scalar round trip under the vector loads instead of one behind the barrier)
     formed_here_v(th, H);
     formed_here_s(I.iceseg, I.n_ratio, M.A_ice, M.r2d, G.ld, table);
+    if constexpr (FIRN) formed_here_s(*F);
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
       const unsigned t = threadIdx.x + j * BS;
       if (whole || t < (1u << kLogTableBits)) *reinterpret_cast<double2*>(&s_logtab[t][0]) = e[j];
     }
     __syncthreads();
-    if (live) table_ray_warm<SC1>(M, I, G, k, H, th, rd, rf, table, &s_logtab[0][0]);
+    if (live) table_ray_warm<SC1, FIRN>(M, I, G, k, H, th, rd, rf, table, &s_logtab[0][0], F);
     return;
   }
 #pragma unroll
@@ -344,7 +355,7 @@ __device__ __forceinline__ void table_block(const DevMedium& M, const IceConsts&
     __builtin_assume(top_hi >= 0);
     if (k < G.n) {
       const int r = ray_row(G, k);
-      table_ray<A1, SC1>(M, I, G, rows[r - r0], r, k, table, full, &s_logtab[0][0], top_hi);
+      table_ray<A1, SC1>(M, I, G, rows[r - r0], r, k, table, full, &s_logtab[0][0], top_hi, F);
     }
   }
   if (TRACE && lane == 0) {
@@ -394,6 +405,29 @@ __global__ __launch_bounds__(kTableBlock) __attribute__((amdgpu_waves_per_eu(kTa
   a = __builtin_amdgcn_readfirstlane(a);
   table_block<false, A1, SC1>(M, Iv[a], Gv[a], map.table[a], nullptr, nullptr,
                          blockIdx.x - (unsigned)map.begin[a]);
+}
+
+// The table kernels in a two-layer firn: the same block bodies with the lower leg's
+// constants F beside IceConsts (per antenna in the multi-antenna launch; F.below is block-uniform,
+// so one launch mixes antennas above and below the boundary).  The air part kernel is shared: it
+// reads nothing of the ice below the surface.
+template <bool A1, bool SC1, bool WARM = false>
+__global__ __launch_bounds__(kTableBlock) __attribute__((amdgpu_waves_per_eu(kTableWaves, kTableWaves))) void table_firn_kernel(
+    DevMedium M, IceConsts I, FirnLeg F, TableArgs G, float* __restrict__ table,
+    double* __restrict__ full) {
+  table_block<false, A1, SC1, WARM ? kTableWarm : kTableFull, true>(M, I, G, table, full, nullptr,
+                                                                    blockIdx.x, &F);
+}
+
+template <bool A1, bool SC1>
+__global__ __launch_bounds__(kTableBlock) __attribute__((amdgpu_waves_per_eu(kTableWaves, kTableWaves))) void table_multi_firn_kernel(
+    DevMedium M, const IceConsts* __restrict__ Iv, const FirnLeg* __restrict__ Fv,
+    const TableArgs* __restrict__ Gv, MultiMap map) {
+  int a = 0;
+  for (int j = 1; j < map.n_ant; ++j) a += (int)blockIdx.x >= map.begin[j];
+  a = __builtin_amdgcn_readfirstlane(a);
+  table_block<false, A1, SC1, kTableFull, true>(M, Iv[a], Gv[a], map.table[a], nullptr, nullptr,
+                                                blockIdx.x - (unsigned)map.begin[a], &Fv[a]);
 }
 
 // Row constants of a whole grid (row_consts_cached): one row per lane, the table block's own
@@ -555,6 +589,20 @@ __global__ __launch_bounds__(kBlock) void rays_kernel(DevMedium M, IceConsts I,
 #pragma unroll
   for (int c = 0; c < 18; ++c) out[c * ld + k] = d[c];
   if (k == 0) signal_done(sig);  // armed for one-ray calls only
+}
+
+// rays_kernel in a two-layer firn; also the one-ray launch (on one lane).
+__global__ __launch_bounds__(kBlock) void rays_firn_kernel(DevMedium M, IceConsts I, FirnLeg F,
+                                                           const double* __restrict__ launch,
+                                                           const double* __restrict__ txh,
+                                                           int in_ice, long long n,
+                                                           double* __restrict__ out, size_t ld) {
+  const long long k = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (k >= n) return;
+  double d[18];
+  ray_solution(M, I, launch[k], txh[k], in_ice != 0, d, true, &F);
+#pragma unroll
+  for (int c = 0; c < 18; ++c) out[c * ld + k] = d[c];
 }
 
 static_assert(kMaxAntennas < (int)kCacheSets, "a multi-antenna launch never evicts its own entries");
@@ -753,7 +801,8 @@ static void table_args(TableArgs& A, const airice_grid& g, size_t ld, int rows_p
 }
 
 int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, int row_begin,
-                 int row_count, float* d_table, double* d_full, size_t ld, hipStream_t st) {
+                 int row_count, float* d_table, double* d_full, size_t ld, hipStream_t st,
+                 const FirnLeg* F) {
   if (row_count <= 0 || g->angle_steps <= 0) return AIRICE_OK;
   TableArgs A;
   table_args(A, *g, ld, table_rows_per_block(g->angle_steps));
@@ -761,7 +810,8 @@ int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, i
   const bool fill_first = (long long)row_count * g->angle_steps >= kFillFirstRays;
   if (int rc = row_consts_cached(M, I, A, st, fill_first, &A.rc)) return rc;
   if (int rc = angle_sines_cached(M, A, st, fill_first, &A.vs)) return rc;
-  static const char* trace_path = getenv("AIRICE_TABLE_TRACE");
+  static const char* trace_env = getenv("AIRICE_TABLE_TRACE");
+  const char* trace_path = F != nullptr ? nullptr : trace_env;  // the timeline has no layered form
   // ray indices are 32-bit inside a launch: grids of kMaxLaunchRays or more go in row slabs
   const int max_rows = (int)std::max<long long>(1, (kMaxLaunchRays - 2 * kTableBlock) / g->angle_steps);
   // a plain build (11 columns, one launch) of a launch seen before reads its rays' air part from
@@ -791,8 +841,18 @@ int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, i
                       : (sc1 ? table_kernel<false, false, true> : table_kernel<false, false, false>);
       if (A.air != nullptr)
         kern = sc1 ? table_kernel<false, false, true, true> : table_kernel<false, false, false, true>;
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(kTableBlock), A.air != nullptr ? 0 : lds, st, M,
-                         I, A, tab, full, nullptr);
+      if (F != nullptr) {
+        const bool a1 = M.A_air == 1.0;
+        auto fkern = a1 ? (sc1 ? table_firn_kernel<true, true> : table_firn_kernel<true, false>)
+                        : (sc1 ? table_firn_kernel<false, true> : table_firn_kernel<false, false>);
+        if (A.air != nullptr)
+          fkern = sc1 ? table_firn_kernel<false, true, true> : table_firn_kernel<false, false, true>;
+        hipLaunchKernelGGL(fkern, dim3(blocks), dim3(kTableBlock), A.air != nullptr ? 0 : lds, st,
+                           M, I, *F, A, tab, full);
+      } else {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(kTableBlock), A.air != nullptr ? 0 : lds, st,
+                           M, I, A, tab, full, nullptr);
+      }
       ktimer_end(KT_TABLE, st);
       if (hipGetLastError() != hipSuccess) return AIRICE_EHIP;
       continue;
@@ -820,8 +880,10 @@ int launch_table(const DevMedium& M, const IceConsts& I, const airice_grid* g, i
 // a's constants and grid (the rows it holds: grids[a].table_rows); tables[a] its output, column
 // stride lds[a].  The per-antenna constants live in a device buffer per distinct set, kept for
 // repeated launches of the same set (bench steps, repeated builds).
+// Fh (nullable): antenna a's lower firn leg; the launch then runs table_multi_firn_kernel.
 int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_grid* grids, int n,
-                       float* const* tables, const size_t* lds, hipStream_t st) {
+                       float* const* tables, const size_t* lds, hipStream_t st,
+                       const FirnLeg* Fh) {
   if (n <= 0) return AIRICE_OK;
   if (n > kMaxAntennas) {
     set_error("at most %d antennas per multi-antenna launch", kMaxAntennas);
@@ -862,10 +924,12 @@ int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_gri
   if (blocks == 0) return AIRICE_OK;
   // the device copy of the per-antenna constants (ConstSetCache; the lock is held)
   static ConstSetCache const_sets;
-  const size_t bytes_i = sizeof(IceConsts) * n, bytes = bytes_i + sizeof(TableArgs) * n;
+  const size_t bytes_i = sizeof(IceConsts) * n, bytes_ia = bytes_i + sizeof(TableArgs) * n;
+  const size_t bytes = bytes_ia + (Fh != nullptr ? sizeof(FirnLeg) * n : 0);
   std::vector<unsigned char> packed(bytes);
   std::memcpy(packed.data(), Ih, bytes_i);
   std::memcpy(packed.data() + bytes_i, Ah.data(), sizeof(TableArgs) * n);
+  if (Fh != nullptr) std::memcpy(packed.data() + bytes_ia, Fh, sizeof(FirnLeg) * n);
   void* dconst = nullptr;
   if (int rc = const_sets.get(packed, stream_capturing(st), &dconst)) {
     if (rc == AIRICE_EINVAL)
@@ -877,6 +941,18 @@ int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_gri
   const bool sc1 = (long long)blocks * kTableBlock < kAgentStoreRays;
   auto multi = M.A_air == 1.0 ? (sc1 ? table_multi_kernel<true, true> : table_multi_kernel<true, false>)
                               : (sc1 ? table_multi_kernel<false, true> : table_multi_kernel<false, false>);
+  if (Fh != nullptr) {
+    auto fmulti = M.A_air == 1.0
+                      ? (sc1 ? table_multi_firn_kernel<true, true> : table_multi_firn_kernel<true, false>)
+                      : (sc1 ? table_multi_firn_kernel<false, true> : table_multi_firn_kernel<false, false>);
+    unsigned char* dc = static_cast<unsigned char*>(dconst);
+    return bracket_launch(LC_TABLE, KT_TABLE, st, [&] {
+      hipLaunchKernelGGL(fmulti, dim3((unsigned)blocks), dim3(kTableBlock), lds_bytes, st, M,
+                         reinterpret_cast<const IceConsts*>(dc),
+                         reinterpret_cast<const FirnLeg*>(dc + bytes_ia),
+                         reinterpret_cast<const TableArgs*>(dc + bytes_i), map);
+    });
+  }
   return bracket_launch(LC_TABLE, KT_TABLE, st, [&] {
     hipLaunchKernelGGL(multi, dim3((unsigned)blocks), dim3(kTableBlock), lds_bytes, st, M,
                        static_cast<const IceConsts*>(dconst),
@@ -887,8 +963,13 @@ int launch_table_multi(const DevMedium& M, const IceConsts* Ih, const airice_gri
 }
 
 int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
-                int in_ice, size_t n, double* out, size_t ld, hipStream_t st) {
+                int in_ice, size_t n, double* out, size_t ld, hipStream_t st, const FirnLeg* F) {
   if (n == 0) return AIRICE_OK;
+  if (F != nullptr)  // a layered firn: rays_firn_kernel for every n (one ray: one lane)
+    return bracket_launch(LC_RAYS, kNoTimer, st, [&] {
+      hipLaunchKernelGGL(rays_firn_kernel, dim3(grid_for((long long)n)), dim3(kBlock), 0, st, M, I,
+                         *F, launch, txh, in_ice, (long long)n, out, ld);
+    });
   if (n == 1)  // one ray: spread over a wave (ray_solution_wave)
     return bracket_launch(LC_SCALAR_RAY, kNoTimer, st, [&] {
       hipLaunchKernelGGL(scalar_ray_kernel, dim3(1), dim3(64), 0, st, M, I, launch, txh, in_ice,
@@ -906,7 +987,8 @@ int launch_rays(const DevMedium& M, const IceConsts& I, const double* launch, co
 // ~1 ulp of them).  A one-ray launch costs a kernel dispatch and a completion wait (~8 us); the
 // host ray takes ~1 us.
 void rays_host(const DevMedium& M, const IceConsts& I, const double* launch, const double* txh,
-               int in_ice, size_t n, double* out, size_t ld) {
+               int in_ice, size_t n, double* out, size_t ld, const FirnLeg* F) {
+  if (F != nullptr) return rays_host_firn(M, I, *F, launch, txh, in_ice, n, out, ld);
   for (size_t k = 0; k < n; ++k) {
     double d[18];
     ray_solution(M, I, launch[k], txh[k], in_ice != 0, d);

@@ -260,7 +260,8 @@ int MakeAtmosphere() {
   return 0;
 }
 
-// GetB_ice / GetC_ice (.cc:150-185; TransitionBoundary is 0) and the air model scan (.cc:216-263)
+// GetB_ice / GetC_ice (.cc:150-185; TransitionBoundary is 0 here: the two-layer firn is
+// MakeRayTracingTablesLayered) and the air model scan (.cc:216-263)
 double GetB_ice(double) { return B_ice; }
 double GetC_ice(double) { return C_ice; }
 double Getnz_ice(double z) {
@@ -465,7 +466,9 @@ int MakeRayTracingTable(double AntennaDepth, double IceLayerHeight, int AntennaN
   return 0;
 }
 
-int MakeRayTracingTables(const std::vector<double>& AntennaDepth, double IceLayerHeight) {
+// firn (nullable): the two-layer firn of MakeRayTracingTablesLayered
+static int make_tables(const std::vector<double>& AntennaDepth, double IceLayerHeight,
+                       const airice_firn* firn) {
   const size_t na = AntennaDepth.size();
   if (na == 0) return 0;
   MakeAtmosphere();
@@ -495,9 +498,13 @@ int MakeRayTracingTables(const std::vector<double>& AntennaDepth, double IceLaye
     }
   for (size_t s = 0; s < lg.size(); s += 32) {
     const int cnt = (int)std::min<size_t>(32, lg.size() - s);
-    if (airice_table_launch_multi(&m, lg.data() + s, cnt, lt.data() + s, ll.data() + s, nullptr) !=
-        AIRICE_OK)
-      die("MakeRayTracingTables");
+    const int rc =
+        firn != nullptr
+            ? airice_table_launch_multi_firn(&m, firn, lg.data() + s, cnt, lt.data() + s,
+                                             ll.data() + s, nullptr)
+            : airice_table_launch_multi(&m, lg.data() + s, cnt, lt.data() + s, ll.data() + s,
+                                        nullptr);
+    if (rc != AIRICE_OK) die("MakeRayTracingTables");
   }
   for (size_t a = 0; a < na; ++a) {
     std::vector<std::vector<float>> cols(11, std::vector<float>(n[a]));
@@ -521,6 +528,15 @@ int MakeRayTracingTables(const std::vector<double>& AntennaDepth, double IceLaye
   LoopStopHeight = g.stop_height;
   TotalHeightSteps = g.height_steps;
   return 0;
+}
+
+int MakeRayTracingTables(const std::vector<double>& AntennaDepth, double IceLayerHeight) {
+  return make_tables(AntennaDepth, IceLayerHeight, nullptr);
+}
+
+int MakeRayTracingTablesLayered(const std::vector<double>& AntennaDepth, double IceLayerHeight,
+                                const airice_firn& firn) {
+  return make_tables(AntennaDepth, IceLayerHeight, &firn);
 }
 
 // ---- table walks (.cc:997-1302) on the host ------------------------------------------------

@@ -72,9 +72,11 @@ def dedupe_depths(depths_cm):
 class AntennaTables:
     """What ``AirIceSolver.antenna_tables`` returns: the distinct antennas' packed device tables
     (``tables``: LookupTable descriptions, ``buffers``: their 11 x n float32 tensors, ``grids``),
-    ``antenna_table`` (each antenna's index into them) and ``depths_cm``."""
+    ``antenna_table`` (each antenna's index into them) and ``depths_cm``.  ``firn``: the two-layer
+    firn the tables were traced in, or None."""
 
-    def __init__(self, solver, ice_cm, grids, buffers, tables, antenna_table, depths_cm):
+    def __init__(self, solver, ice_cm, grids, buffers, tables, antenna_table, depths_cm,
+                 firn=None):
         self.solver = solver
         self.ice_cm = float(ice_cm)
         self.grids = grids
@@ -82,11 +84,14 @@ class AntennaTables:
         self.tables = tables
         self.antenna_table = list(antenna_table)
         self.depths_cm = [float(d) for d in depths_cm]
+        self.firn = firn
 
     def lookup(self, src_cm, dist_cm, stream=None):
         """GetHorizontalDistanceToIntersectionPoint_Table of every (antenna, source) pair in one
         launch: ``src_cm`` (n_src) and ``dist_cm`` (n_ant, n_src) float64 device tensors.  Returns
-        (out (9, n_ant, n_src) float64, ok (n_ant, n_src) uint8, flags (n_ant, n_src) uint8)."""
+        (out (9, n_ant, n_src) float64, ok (n_ant, n_src) uint8, flags (n_ant, n_src) uint8).
+        With a firn the minimizer fallback is not available (it is one-layer): lanes flagged
+        LOOKUP_FALLBACK come back as NaN with ok = 0."""
         import torch
         n_ant, n_src = len(self.depths_cm), int(src_cm.numel())
         dev = src_cm.device
@@ -96,6 +101,13 @@ class AntennaTables:
         self.solver.table_lookup_multi_device(self.tables, self.antenna_table, self.depths_cm,
                                               src_cm, dist_cm, self.ice_cm, out, ok, flags,
                                               stream=stream)
+        if self.firn is not None:
+            import contextlib
+            ctx = contextlib.nullcontext() if stream is None else torch.cuda.stream(stream)
+            with ctx:
+                fb = (flags & _lib.LOOKUP_FALLBACK) != 0
+                out.masked_fill_(fb.unsqueeze(0), float("nan"))
+                ok.masked_fill_(fb, 0)
         return out, ok, flags
 
 
@@ -232,36 +244,58 @@ class AirIceSolver:
 
     # ------------------------------------------------------------------ table
     def table_device(self, grid: Grid, table, full=None, row_begin: int = 0,
-                     row_count: int | None = None, ld: int | None = None, stream=None) -> None:
+                     row_count: int | None = None, ld: int | None = None, stream=None,
+                     firn=None) -> None:
+        """airice_table_launch; with ``firn`` (a ``Firn``) airice_table_launch_firn: the two-layer
+        firn, this medium's A_ice with the firn's B and C."""
         if row_count is None:
             row_count = grid.table_rows - row_begin
         n = row_count * grid.angle_steps
         ld = n if ld is None else ld
+        if firn is not None:
+            check(lib().airice_table_launch_firn(ctypes.byref(self.medium), ctypes.byref(firn),
+                                                 ctypes.byref(grid), row_begin, row_count,
+                                                 ptr(table), ptr(full), ld,
+                                                 _stream_handle(stream)),
+                  "airice_table_launch_firn")
+            return
         check(lib().airice_table_launch(ctypes.byref(self.medium), ctypes.byref(grid), row_begin,
                                         row_count, ptr(table), ptr(full), ld,
                                         _stream_handle(stream)), "airice_table_launch")
 
-    def tables_device(self, grids, tables, stream=None) -> None:
+    def tables_device(self, grids, tables, stream=None, firn=None) -> None:
         """Several antennas' whole tables in one launch (airice_table_launch_multi): grids[a] and
         tables[a] (11 x >= grids[a].n_rays float32 device tensors, one per antenna)."""
         n = len(grids)
         garr = (Grid * n)(*grids)
         ptrs = (ctypes.c_void_p * n)(*[ptr(t).value for t in tables])
         lds = (ctypes.c_size_t * n)(*[int(t.shape[-1]) for t in tables])
+        if firn is not None:
+            check(lib().airice_table_launch_multi_firn(ctypes.byref(self.medium),
+                                                       ctypes.byref(firn), garr, n, ptrs, lds,
+                                                       _stream_handle(stream)),
+                  "airice_table_launch_multi_firn")
+            return
         check(lib().airice_table_launch_multi(ctypes.byref(self.medium), garr, n, ptrs, lds,
                                               _stream_handle(stream)),
               "airice_table_launch_multi")
 
     def table_host(self, grid: Grid, row_begin: int = 0, row_count: int | None = None,
-                   full: bool = False):
+                   full: bool = False, firn=None):
         if row_count is None:
             row_count = grid.table_rows - row_begin
         n = row_count * grid.angle_steps
         table = np.empty((_lib.TABLE_COLUMNS, n), dtype=np.float32)
         fullarr = np.empty((_lib.RAY_FIELDS, n), dtype=np.float64) if full else None
-        check(lib().airice_table_host(ctypes.byref(self.medium), ctypes.byref(grid), row_begin,
-                                      row_count, ptr(table), ptr(fullarr), n),
-              "airice_table_host")
+        if firn is not None:
+            check(lib().airice_table_host_firn(ctypes.byref(self.medium), ctypes.byref(firn),
+                                               ctypes.byref(grid), row_begin, row_count,
+                                               ptr(table), ptr(fullarr), n),
+                  "airice_table_host_firn")
+        else:
+            check(lib().airice_table_host(ctypes.byref(self.medium), ctypes.byref(grid),
+                                          row_begin, row_count, ptr(table), ptr(fullarr), n),
+                  "airice_table_host")
         return (table, fullarr) if full else table
 
     # ------------------------------------------------------------------ table files
@@ -301,19 +335,33 @@ class AirIceSolver:
 
     # ------------------------------------------------------------------ rays
     def rays_device(self, launch_deg, txh, ice_h: float, depth: float, in_ice: bool, out,
-                    ld: int | None = None, stream=None) -> None:
+                    ld: int | None = None, stream=None, firn=None) -> None:
         n = int(launch_deg.numel())
+        if firn is not None:
+            check(lib().airice_rays_launch_firn(ctypes.byref(self.medium), ctypes.byref(firn),
+                                                ptr(launch_deg), ptr(txh), ice_h, depth,
+                                                int(in_ice), n, ptr(out), n if ld is None else ld,
+                                                _stream_handle(stream)),
+                  "airice_rays_launch_firn")
+            return
         check(lib().airice_rays_launch(ctypes.byref(self.medium), ptr(launch_deg), ptr(txh),
                                        ice_h, depth, int(in_ice), n, ptr(out),
                                        n if ld is None else ld, _stream_handle(stream)),
               "airice_rays_launch")
 
-    def rays_host(self, launch_deg, txh, ice_h: float, depth: float, in_ice: bool) -> np.ndarray:
+    def rays_host(self, launch_deg, txh, ice_h: float, depth: float, in_ice: bool,
+                  firn=None) -> np.ndarray:
         """airice_rays_host: GetRayTracingSolutions for host arrays on the CPU (the one-query
         drop-in's path, same source as the device kernels); (18, n) doubles."""
         a = np.ascontiguousarray(launch_deg, dtype=np.float64).ravel()
         h = np.ascontiguousarray(np.broadcast_to(txh, a.shape), dtype=np.float64).ravel()
         out = np.empty((_lib.RAY_FIELDS, a.size), dtype=np.float64)
+        if firn is not None:
+            check(lib().airice_rays_host_firn(ctypes.byref(self.medium), ctypes.byref(firn),
+                                              ptr(a), ptr(h), ice_h, depth, int(in_ice), a.size,
+                                              ptr(out), max(a.size, 1)),
+                  "airice_rays_host_firn")
+            return out
         check(lib().airice_rays_host(ctypes.byref(self.medium), ptr(a), ptr(h), ice_h, depth,
                                      int(in_ice), a.size, ptr(out), max(a.size, 1)),
               "airice_rays_host")
@@ -442,7 +490,7 @@ class AirIceSolver:
 
     def antenna_tables(self, depths_cm, ice_cm: float, height_step: float = 10.0,
                        start_angle: float = 90.1, stop_angle: float = 180.0,
-                       angle_step: float = 0.1, stream=None) -> AntennaTables:
+                       angle_step: float = 0.1, stream=None, firn=None) -> AntennaTables:
         """The tables of a set of antennas, ready for ``AntennaTables.lookup``: antennas at the
         same depth share one table (``dedupe_depths``, as the reference); the distinct tables are
         made in one ``tables_device`` launch and packed."""
@@ -453,11 +501,12 @@ class AirIceSolver:
                  for d in distinct]
         buffers = [torch.empty((_lib.TABLE_COLUMNS, g.n_rays), dtype=torch.float32, device=dev)
                    for g in grids]
-        self.tables_device(grids, buffers, stream=stream)
+        self.tables_device(grids, buffers, stream=stream, firn=firn)
         tables = [self.lookup_table(b, g) for b, g in zip(buffers, grids)]
         for t in tables:
             self.lookup_pack(t, stream=stream)
-        return AntennaTables(self, ice_cm, grids, buffers, tables, antenna_table, depths_cm)
+        return AntennaTables(self, ice_cm, grids, buffers, tables, antenna_table, depths_cm,
+                             firn=firn)
 
     # ------------------------------------------------------------------ single ray (cfg1)
     def single_ray_host(self, antenna_depth: float, launch_deg: float, txh: float, ice: float,

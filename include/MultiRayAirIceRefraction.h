@@ -48,6 +48,7 @@
 #include <cstddef>
 #include <vector>
 
+#include "airice.h" /* airice_firn (MakeRayTracingTablesLayered) */
 #include "airice_gsl_roots.h"
 
 /* Defined by the caller (reference .h:23-24, RunMultiRayCode.C:3-4). */
@@ -197,6 +198,13 @@ bool GetHorizontalDistanceToIntersectionPoint_Table(
  * reference's per-antenna loop of MakeRayTracingTable calls would (RunMultiRayCode.C:29-52), with
  * one launch ramp and drain for all of them.  The grid globals are those of the last antenna. */
 int MakeRayTracingTables(const std::vector<double>& AntennaDepth, double IceLayerHeight);
+/* The same in a two-layer (double-exponential) firn (airice_table_launch_multi_firn, airice.h):
+ * the reference's TransitionBoundary != 0 model as the physical piecewise profile, with A_ice of
+ * the namespace data and the firn's B and C (B_ice / C_ice are not read).  The minimizer stays
+ * one-layer: a lookup of such a table that reaches the reference's minimizer fallback (.cc:1418)
+ * is answered in the one-layer model of A_ice / B_ice / C_ice. */
+int MakeRayTracingTablesLayered(const std::vector<double>& AntennaDepth, double IceLayerHeight,
+                                const airice_firn& firn);
 /* The same lookup on an already-resolved table index (AllTableAllAntData[TableIndex]). */
 bool TableLookup(double SrcHeightASL, double HorizontalDistanceToRx,
                  double RxDepthBelowIceBoundary, double IceLayerHeight, int TableIndex,

@@ -153,6 +153,43 @@ int airice_rays_host(const airice_medium *m, const double *launch_deg, const dou
                      double ice_h_m, double depth_m, int32_t in_ice, size_t n, double *out,
                      size_t ld);
 
+/* --- two-layer (double-exponential) firn ---------------------------------- */
+/* The reference's second ice model (TransitionBoundary != 0, GetB_ice / GetC_ice .cc:150-185, the
+ * two-layer ice leg of GetRayTracingSolutions .cc:1923-1990), as the physical piecewise profile:
+ * the lower layer's B and C at both ends of the lower segment, the sine stepping by
+ * n_up(b) / n_low(b) across the boundary (DESIGN.md §14 for the difference from the reference).
+ * The *_firn entry points take the arguments of their namesakes plus the firn after the medium,
+ * with the same output layouts and stream semantics; they use m->A_ice and ignore m->B_ice and
+ * m->C_ice.  An antenna at or above the boundary (|depth| <= boundary_m) or in the air gives the
+ * bits of the one-layer call with (A_ice, B[0], C[0]).  A NULL firn, a non-finite field,
+ * boundary_m <= 0 or C[l] <= 0 returns AIRICE_EINVAL and writes nothing.
+ * Known limit: the minimizer is one-layer.  airice_solve_*, airice_hdtip_* have no firn form, and a
+ * lookup (airice_lookup_*) of a layered table reads the table correctly but answers its lanes
+ * flagged AIRICE_LOOKUP_FALLBACK in the one-layer model of m: treat those lanes as unanswered.
+ * airice_table_save does not record the firn: do not save a layered table yet. */
+typedef struct airice_firn {   /* n(z) = m->A_ice + B[l] exp(-C[l] z), z >= 0 the depth in m; */
+  double boundary_m;           /* l = 0 for z <= boundary_m, l = 1 below; > 0 and finite        */
+  double B[2], C[2];           /* finite, C > 0                                                  */
+} airice_firn;
+#define AIRICE_FIRN_SUMMIT {14.9, {-0.5019, -0.448023}, {0.03247, 0.02469}}  /* with A_ice = 1.775 */
+double airice_nz_firn(const airice_medium *m, const airice_firn *f, double z);
+int airice_table_launch_firn(const airice_medium *m, const airice_firn *f, const airice_grid *g,
+                             int32_t row_begin, int32_t row_count, float *d_table, double *d_full,
+                             size_t ld, void *stream);
+int airice_table_launch_multi_firn(const airice_medium *m, const airice_firn *f,
+                                   const airice_grid *grids, int32_t n_grids,
+                                   float *const *d_tables, const size_t *lds, void *stream);
+int airice_table_host_firn(const airice_medium *m, const airice_firn *f, const airice_grid *g,
+                           int32_t row_begin, int32_t row_count, float *h_table, double *h_full,
+                           size_t ld);
+int airice_rays_launch_firn(const airice_medium *m, const airice_firn *f,
+                            const double *d_launch_deg, const double *d_txh, double ice_h_m,
+                            double depth_m, int32_t in_ice, size_t n, double *d_out, size_t ld,
+                            void *stream);
+int airice_rays_host_firn(const airice_medium *m, const airice_firn *f, const double *launch_deg,
+                          const double *txh, double ice_h_m, double depth_m, int32_t in_ice,
+                          size_t n, double *out, size_t ld);
+
 /* Where one-query calls run: AIRICE_SCALAR_HOST (default: the calling CPU thread, from the same
  * __host__ __device__ source as the kernels, with the host's correctly rounded sqrt and quotients,
  * so within about an ulp of the same query inside a GPU batch) or AIRICE_SCALAR_DEVICE (a
